@@ -11,8 +11,18 @@ and run a frame through it (``train_dp_path``), else over the RCCL communicator 
 is kept beside it (``train_step_allreduce_ms``). The weak-scaling figures (2^21 queries per GPU) are kept as the extra key
 ``weak``.
 
-Launch: ``python bench.py [--gpus N --steps K --warmup W]``. N > 1 either under torch.distributed.run (WORLD_SIZE set) or
-on its own: with WORLD_SIZE unset the process starts N fresh child processes of itself (one rank per GPU, RANK /
+A plain run (``python bench.py [--gpus N --steps K --warmup W]``) does only what ``value`` needs: set-up, warm-up, the K
+timed inference steps and the result line (``value``, ``ms_per_step``, the timed kernel's roofline). ``--full`` (or
+``NRC_BENCH_FULL=1`` in the environment, for scripts that wrap a whole command line) adds every other leg -- the
+training steps, the sustained run, configs[3] at N = 1, the post-trace frame, the width-128 and
+Hash models, tiny-cuda-nn's numerics, the CPU baseline with its parity check, and at N > 1 the weak-scaling and
+peer-exchange figures -- under the same keys as before (null in a plain run). ``--dump-outputs DIR`` writes the
+radiance the last timed step left in the caller's output buffer as ``DIR/radiance.npy`` (``radiance_rank<r>.npy`` at
+N > 1; float32, one row per query): the queries, the initial weights and the training frames before the timed steps are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Launch: ``python bench.py [--gpus N --steps K --warmup W] [--full]``. N > 1 either under torch.distributed.run
+(WORLD_SIZE set) or on its own: with WORLD_SIZE unset the process starts N fresh child processes of itself (one rank per GPU, RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in their environment) before it makes any GPU call, passes rank 0's
 JSON line through and exits non-zero if any rank fails (``launch_ranks``).
 """
@@ -46,12 +56,21 @@ QUERIES_C4 = 1 << 22  # configs[3]: the 2K frame, sharded over the ranks
 ROUND = "r06"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--queries", type=int, default=QUERIES_PER_GPU, help="queries per GPU per step")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("NRC_BENCH_FULL") == "1",
+                    help="(or NRC_BENCH_FULL=1 in the environment) after the timed steps also measure everything "
+                         "beyond the headline figure (training steps, sustained run, configs[3], post-trace frame, width-128 / Hash models, tiny-cuda-nn numerics, "
+                         "CPU baseline and parity; N > 1: weak scaling, peer exchange); --train-frames, --cpu-seconds, "
+                         "--sustained, --frame-iters and the --no-* options select among those legs and have no "
+                         "effect without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output buffer of the last timed step to DIR/radiance.npy (float32, one row per "
+                         "query; radiance_rank<r>.npy for N > 1)")
     ap.add_argument("--train-frames", type=int, default=20, help="timed frames of 4 x 16384 training")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample duration")
     ap.add_argument("--no-cpu", action="store_true")
@@ -71,7 +90,12 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse several ranks on one "
                          "GPU, which is not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run times the headline inference only: every optional leg off
+        args.no_cpu = args.no_wide = args.no_hash = args.no_c4 = args.no_peer = True
+        args.sustained = args.frame_iters = 0
+    return args
 
 
 def cpu_baseline(queries: np.ndarray, params: np.ndarray, target_s: float, train_batch, gpu_out=None) -> dict:
@@ -693,7 +717,7 @@ def launch_ranks(cmd: list[str], world: int, port: int | None = None, poll_s: fl
     return 128 - rc if rc < 0 else rc
 
 
-def self_launch(args) -> int | None:
+def self_launch(args, argv) -> int | None:
     """--gpus N > 1 without a launcher (WORLD_SIZE unset): N fresh children of this script. Called before anything
     touches the GPU; torch.cuda.device_count() does not initialise HIP on this image. None: run in this process."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
@@ -707,12 +731,13 @@ def self_launch(args) -> int | None:
                   f"found {have} (one rank per GPU; --dist-backend gloo rehearses ranks sharing a GPU)",
                   file=sys.stderr, flush=True)
             return 2
-    return launch_ranks([sys.executable, str(Path(__file__).resolve()), *sys.argv[1:]], args.gpus)
+    return launch_ranks([sys.executable, str(Path(__file__).resolve()), *argv], args.gpus)
 
 
-def main() -> None:
-    args = parse()
-    rc = self_launch(args)
+def main(argv=None) -> None:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse(argv)
+    rc = self_launch(args, argv)
     if rc is not None:
         raise SystemExit(rc)
     import torch
@@ -838,10 +863,15 @@ def main() -> None:
     value = nq_total * args.steps / wall_max / 1e6
     # the weights the timed inference used (training below moves them), for the CPU leg's parity check
     infer_params = net.get_state(nrc.StateSlot.INFER) if rank == 0 and world == 1 and not args.no_cpu else None
-    out_np = out.cpu().numpy() if infer_params is not None else None
+    out_np = out.cpu().numpy() if infer_params is not None or args.dump_outputs else None
+    if args.dump_outputs:
+        # what the last timed step left in the caller's buffer, before any later leg writes to it again
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        np.save(dump_dir / ("radiance.npy" if world == 1 else f"radiance_rank{rank}.npy"), out_np)
 
     weak = None
-    if c4:
+    if c4 and args.full:
         # weak scaling (the r01 line): 2^21 queries per GPU
         nw = QUERIES_PER_GPU
         qw = torch.from_numpy(nrc.synthetic.cornell_queries(nw, seed=seed)).to(dev)
@@ -885,10 +915,12 @@ def main() -> None:
         barrier()
         return max_over_ranks(time.perf_counter() - t0) / args.train_frames * 1e3
 
-    train_frame_ms = time_train_frames()
-    train_step_ms = train_frame_ms / 4
+    train_frame_ms = time_train_frames() if args.full else None
+    train_step_ms = train_frame_ms / 4 if args.full else None
     train_step_allreduce_ms = None
-    if train_dp_path == "peer exchange":
+    if not args.full:
+        train_dp_path = None
+    elif train_dp_path == "peer exchange":
         net.peer_exchange_close()  # the same frames over the all-reduce path (RCCL), for comparison
         peer["on"] = False
         barrier()
@@ -899,7 +931,7 @@ def main() -> None:
     # the same training frames replayed from a HIP graph (N = 1): the GPU's own step time, without the per-call host
     # cost (Python + ctypes + one hipLaunchKernel per kernel) that the eager figure above includes
     train_step_graph_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         train_step_graph_ms = graph_ms_per_call(net, stream, lambda i: net.train(frames_q[(i // 4) % 4][(i % 4) * nrc.BATCH_SIZE:],
                                                                                 frames_t[(i // 4) % 4][(i % 4) * nrc.BATCH_SIZE:]), 16, 10)
 
@@ -953,7 +985,7 @@ def main() -> None:
 
     wide = None if args.no_wide else wide_bench(nrc, dev, world, rank, max(10, args.steps // 4), barrier)
     hashgrid = hash_bench(nrc, dev, max(10, args.steps // 10)) if world == 1 and not args.no_hash else None
-    tcnn_numerics = tcnn_numerics_bench(nrc, net, q, out, nq, max(10, args.steps // 10)) if world == 1 else None
+    tcnn_numerics = tcnn_numerics_bench(nrc, net, q, out, nq, max(10, args.steps // 10)) if world == 1 and args.full else None
 
     achieved = FLOP_PER_QUERY * nq / (kernel_ms * 1e-3) / 1e12
     if c4:
@@ -971,6 +1003,7 @@ def main() -> None:
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "strong" if c4 else "weak",

@@ -1,23 +1,28 @@
 """Every `file:line` citation of a reference source in this repo resolves.
 
-Scans the repo's own sources and docs for citations of files that exist under /root/reference
-(`NRCNetwork.cu:41-56`, `Device.cpp:1504`, and bare continuations such as `(:43, :66)` after a cited file
-on the same line) and checks that every cited line range lies inside the cited file. A few load-bearing
-boundary citations are also checked against the text they must point at. Skipped where /root/reference is
-absent (the GPU box): it is a repository-hygiene check, not part of the product.
+Scans the repo's own sources and docs for citations of the reference's files (`NRCNetwork.cu:41-56`,
+`Device.cpp:1504`, and bare continuations such as `(:43, :66)` after a cited file on the same line) and checks
+that every cited line range lies inside the cited file. A few load-bearing boundary citations are also checked
+against the text they must point at.
+
+The reference tree is not part of this repository, so the test reads an index of it instead,
+tests/golden/reference_index.json: the line count of every citable file, and for each anchor text below the
+numbers of the lines that hold it (no reference text beyond the anchors' own few words). With a checkout of the
+reference at hand, `python tests/test_citations.py <reference root>` writes the index again.
 """
 from __future__ import annotations
 
+import functools
+import json
 import os
 import re
+import sys
 from pathlib import Path
 
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-REF = Path("/root/reference")
-
-pytestmark = pytest.mark.skipif(not REF.is_dir(), reason="reference tree not present")
+INDEX = ROOT / "tests" / "golden" / "reference_index.json"
 
 SCAN_SUFFIXES = {".py", ".h", ".hpp", ".hip", ".cpp", ".c", ".md", ".sh"}
 SKIP_DIRS = {".git", "gpurun_out", "__pycache__", ".pytest_cache", "build"}
@@ -28,18 +33,21 @@ CITE = re.compile(r"(?P<file>[\w./-]+\.(?:cu|h|cpp|txt|gitmodules))(?::(?P<a>\d+
 BARE = re.compile(r"(?<=[\s(`,]):(?P<a>\d+)(?:-(?P<b>\d+))?\b")
 
 
+@functools.lru_cache(maxsize=None)
+def _load_index() -> dict:
+    return json.loads(INDEX.read_text())
+
+
 def _ref_index() -> dict[str, list[Path]]:
+    """Base name -> the reference files of that name (paths relative to the reference root)."""
     idx: dict[str, list[Path]] = {}
-    for dirpath, dirnames, filenames in os.walk(REF):
-        dirnames[:] = [d for d in dirnames if not d.startswith(".") and d != "imgui"]
-        for f in filenames:
-            idx.setdefault(f, []).append(Path(dirpath) / f)
+    for rel in _load_index()["lines"]:
+        idx.setdefault(os.path.basename(rel), []).append(Path(rel))
     return idx
 
 
 def _nlines(p: Path) -> int:
-    with open(p, "rb") as fh:
-        return fh.read().count(b"\n") + 1
+    return _load_index()["lines"][p.as_posix()]
 
 
 def _candidates(idx, cited: str) -> list[Path]:
@@ -116,5 +124,26 @@ ANCHORS = [
 
 @pytest.mark.parametrize("path,a,b,needle", ANCHORS)
 def test_boundary_anchor_text(path, a, b, needle):
-    lines = (REF / path).read_text(errors="replace").splitlines()
-    assert needle in "\n".join(lines[a - 1: b]), f"{path}:{a}-{b} does not contain {needle!r}"
+    held = _load_index()["anchor_lines"][path][needle]  # the lines of `path` that contain `needle`
+    assert any(a <= ln <= b for ln in held), f"{path}:{a}-{b} does not contain {needle!r} (it is on lines {held})"
+
+
+def write_index(ref: Path) -> None:
+    """The index of a reference checkout: line counts of the citable files (the walk and the line count the scan
+    used on the tree itself) and, per anchor, the lines that hold its text."""
+    lines = {}
+    for dirpath, dirnames, filenames in os.walk(ref):
+        dirnames[:] = sorted(d for d in dirnames if not d.startswith(".") and d != "imgui")
+        for f in sorted(filenames):
+            p = Path(dirpath) / f
+            if CITE.fullmatch(f + ":1"):
+                lines[p.relative_to(ref).as_posix()] = p.read_bytes().count(b"\n") + 1
+    anchors: dict[str, dict[str, list[int]]] = {}
+    for path, _, _, needle in ANCHORS:
+        text = (ref / path).read_text(errors="replace").splitlines()
+        anchors.setdefault(path, {})[needle] = [i for i, ln in enumerate(text, 1) if needle in ln]
+    INDEX.write_text(json.dumps({"lines": lines, "anchor_lines": anchors}, indent=0, sort_keys=True) + "\n")
+
+
+if __name__ == "__main__":
+    write_index(Path(sys.argv[1]))

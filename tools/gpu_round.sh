@@ -5,9 +5,11 @@
 #   tools/gpu_round.sh tests [pytest args...]   GPU tests (default: the whole -m gpu suite), then smoke()
 #   tools/gpu_round.sh pytest <paths...>         just the given GPU tests (no smoke)
 #   tools/gpu_round.sh bench                     PMC passes of the bench (HBM bytes -> profiles/pmc_infer_<round>.json on
-#                                                the box), the default bench line, rocprofv3 kernel-trace stats of the bench
-#                                                and of train-only runs (width 64 and 128)
-#   tools/gpu_round.sh bench-line [args...]      one bench.py line (default flags unless given)
+#                                                the box), the whole bench line (bench.py --full, through bench-line),
+#                                                rocprofv3 kernel-trace stats of the bench and of train-only runs
+#                                                (width 64 and 128)
+#   tools/gpu_round.sh bench-line [args...]      one bench.py line with the given flags (none: the plain run, the timed
+#                                                inference only; --full: every leg)
 #   tools/gpu_round.sh ab-infer <n> <variants> [rounds] [iters]   in-process A/B of inference variants (debug library)
 #   tools/gpu_round.sh energy <variants> [rounds]                 J/query A/B of inference variants (debug library)
 #   tools/gpu_round.sh power [power_paths.py args...]             power / clock / nJ per query of the product paths
@@ -49,12 +51,13 @@ pytest)
   run_pytest pytest_sel.log 900 "$@" || exit $?
   ;;
 bench)
-  bash tools/gpu_pmc.sh pmc_bench python3 "$ROOT/bench.py" --steps 10 --warmup 2 --train-frames 2 --no-cpu --sustained 0 --frame-iters 2 --no-wide --no-hash --no-c4 || exit 6
+  bash tools/gpu_pmc.sh pmc_bench python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --train-frames 2 --no-cpu --sustained 0 --frame-iters 2 --no-wide --no-hash --no-c4 || exit 6
   python tools/pmc_to_json.py gpurun_out/pmc_bench infer_kernel gpurun_out/pmc_infer.json > /dev/null || exit 7
   python tools/pmc_summary.py gpurun_out/pmc_bench > gpurun_out/pmc_bench_summary.txt || exit 8
   cp gpurun_out/pmc_infer.json "profiles/pmc_infer_$ROUND.json"
-  timeout -k 10 600 python bench.py > gpurun_out/bench.log 2>&1 || { echo "bench failed"; tail -20 gpurun_out/bench.log; exit 4; }
-  tail -1 gpurun_out/bench.log
+  bash "$ROOT/tools/gpu_round.sh" bench-line --full || exit 4
+  # the profiled run below measures every leg its options name: NRC_BENCH_FULL=1 is bench.py --full
+  export NRC_BENCH_FULL=1
   # --no-c4: the infer kernel's rocprof summary then holds the 2^21-query launches only (the C4 shards'
   # 2^19-query launches had been averaged in); the profiled run prints its own bench line (prof_bench.log)
   cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$ROOT/gpurun_out/prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --train-frames 5 --no-cpu --no-c4 --sustained 200 > "$ROOT/gpurun_out/prof_bench.log" 2>&1 || { echo "rocprof failed"; tail -20 "$ROOT/gpurun_out/prof_bench.log"; exit 5; }
