@@ -50,7 +50,8 @@ typedef struct nrc_config {
     /* Extensions (BASELINE.json configs[4]; not in the reference, whose FullyFusedMLP has 64 neurons): */
     uint32_t width;           /* MLP neurons: 64 (reference) or 128 (NRC_WIDE_*; Frequency / FrequencySH only) */
     uint32_t infer_precision; /* nrc_precision of infer(): F16 (default), F16_ACC16 (tcnn's f16 accumulation, width 64
-                               * Frequency or Hash) or FP8 (width 128 only) */
+                               * Frequency or Hash) or FP8 (width 128; width 64 with Frequency and compact queries:
+                               * Hash, FrequencySH and NRC_QUERY_PADDED return NRC_ERR_UNSUPPORTED there) */
     /* RadianceQuery layout of every query buffer of the handle (the reference's compile-time
      * USE_COMPACT_RADIANCE_QUERY, config.h:113): NRC_QUERY_COMPACT (default, 15 f32) or NRC_QUERY_PADDED (16 f32 with
      * pad_ and its Identity(1) feature, layout.h). Padded: width 64, Frequency or Hash, infer_precision F16; the
@@ -63,7 +64,8 @@ typedef struct nrc_config {
  * F16_ACC16: tiny-cuda-nn's FullyFusedMLP numerics, an f16 accumulator rounded after every 16-wide K chunk in K order
  * (NRCNetworkConfigs.h:26-33; oracle mode ORC_TCNN), about 3-4x slower; infer / infer_stream only.
  * FP8: e4m3 weights (one power-of-two scale per output row) and e4m3 activations on the MX-scaled fp8 MFMA for layers
- * 1..5, layer 0 in f16. */
+ * 1..5, layer 0 in f16; training stays f16. At width 64 the FP8 image is repacked from the inference
+ * weights after every call that changes them, on that call's stream. */
 typedef enum nrc_precision {
     NRC_PRECISION_F16 = 0,
     NRC_PRECISION_FP8 = 1,
@@ -282,7 +284,9 @@ nrc_status nrc_debug_infer_stamps(nrc_net* net, const float* inputs_d, float* ou
 /* Width-128 networks: inference with either precision's weight image (both are packed from the inference
  * weights), regardless of the configured infer_precision (A/B timing and parity tests). Bits 4+ of precision pick a
  * kernel variant of the debug library (Frequency only): 1 = 1024-thread blocks, 2 = FP8 with the ReLU on the
- * converted bytes. */
+ * converted bytes. A width-64 handle configured with NRC_PRECISION_FP8 accepts F16 (the production f16 kernel on its
+ * f16 image) and FP8 (bits 4+: 1 = the two-tiles-per-wave shape of the debug library): one handle gives the A/B. Any
+ * other width-64 handle answers as before (F16_ACC16 where implemented, else NRC_ERR_UNSUPPORTED). */
 nrc_status nrc_debug_infer_precision(nrc_net* net, int precision, const float* inputs_d, float* outputs_d, uint32_t n,
                                      hipStream_t stream);
 /* e4m3 conversion exactly as the FP8 kernels do it: clamp to [relu ? 0 : -448, 448], round to nearest even. */

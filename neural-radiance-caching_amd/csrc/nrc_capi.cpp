@@ -501,6 +501,11 @@ struct nrc_net {
     float *wide_slabs = nullptr, *wide_loss_partials = nullptr;
     int64_t wide_ws_bpad = 0;
 
+    // width-64 FP8 inference (nrc_infer8.hip): FP8 fragments of W1..W5 + row scale words, repacked from the inference
+    // weights after every launch that rewrites them; allocated only when the handle is configured with FP8
+    uint8_t* img8 = nullptr;
+    bool fp8_64() const { return cfg.width == NRC_WIDTH && cfg.infer_precision == NRC_PRECISION_FP8; }
+
     bool hash() const { return encoding == NRC_ENCODING_HASH; }
     bool wide() const { return cfg.width == NRC_WIDE_WIDTH; }
     bool padq() const { return cfg.query_layout == NRC_QUERY_PADDED; }
@@ -537,6 +542,8 @@ struct nrc_net {
         scatter_part = nullptr;
         scatter_part_bytes = 0;
         scatter_blocks = 0;
+        f(img8);
+        img8 = nullptr;
         f(wide_img16); f(wide_img8); f(wide_scales);
         f(wide_fwd_train); f(wide_bwd_train); f(wide_ws_in); f(wide_ws_d); f(wide_slabs); f(wide_loss_partials);
         wide_img16 = wide_img8 = nullptr;
@@ -675,12 +682,19 @@ WideImages wide_images(const nrc_net* net) {
                       net->wide_bwd_train, net->encoding == NRC_ENCODING_FREQUENCY_SH ? 2 : 0};
 }
 
+// FP8-configured width-64 handles: the FP8 image follows the inference weights (after every launch on s that rewrote
+// them); every other handle launches nothing
+void pack_fp8_64(nrc_net* net, hipStream_t s) {
+    if (net->fp8_64()) HIP_CHECK(launch_pack8(net->infer, net->img8, s));
+}
+
 void repack(nrc_net* net, hipStream_t s) {
     if (net->wide()) {
         HIP_CHECK(launch_wide_pack(net->infer, net->params, wide_images(net), s));
         return;
     }
     HIP_CHECK(launch_reduce_adam(kPackOnly, nullptr, 0, nullptr, nullptr, nullptr, net->buffers(), net->optim(1), s));
+    pack_fp8_64(net, s);
     if (net->hash()) HIP_CHECK(launch_grid_adam(kPackOnly, net->grid_buffers(), net->optim(1), s));
 }
 
@@ -832,6 +846,7 @@ void do_train(nrc_net* net, const float* in, const float* tgt, uint32_t b, float
         if (e != hipErrorNotSupported) {
             HIP_CHECK(e);
             net->step += 1;
+            pack_fp8_64(net, net->stream);
             if (loss_h) *loss_h = net->read_loss();
             return;
         }
@@ -840,6 +855,7 @@ void do_train(nrc_net* net, const float* in, const float* tgt, uint32_t b, float
     net->step += 1;
     HIP_CHECK(launch_reduce_adam(kReduceFused, net->slabs, blocks, net->loss_partials, nullptr,
                                  loss_d ? loss_d : net->loss_dev, net->buffers(), net->optim(net->step), net->stream));
+    pack_fp8_64(net, net->stream);
     if (loss_h) {
         *loss_h = net->read_loss();
     }
@@ -877,6 +893,8 @@ hipError_t infer_any(nrc_net* net, const float* in, float* out, uint32_t n) {
         return launch_infer_sh(in, out, n, net->wf_infer, nullptr, nullptr, 0, -1, 1.0f, net->stream);
     if (net->cfg.infer_precision == NRC_PRECISION_F16_ACC16)
         return launch_infer_tcnn(in, out, n, net->wf_infer, net->infer, net->stream);
+    if (net->fp8_64())
+        return launch_infer8(0, in, out, n, net->wf_infer, net->img8, nullptr, nullptr, 0, -1, 1.0f, net->stream);
     return launch_infer(in, out, n, net->wf_infer, net->stream, net->work_queue, &net->pool_parity, net->padq());
 }
 
@@ -1093,8 +1111,13 @@ nrc_status nrc_init(nrc_net* net, hipStream_t stream, int encoding, const nrc_co
             (c.width != NRC_WIDTH || encoding == NRC_ENCODING_FREQUENCY_SH))
             throw ApiError(NRC_ERR_UNSUPPORTED,
                            "F16_ACC16 (tcnn numerics) is implemented for the width-64 Frequency and Hash networks");
-        if (c.infer_precision == NRC_PRECISION_FP8 && c.width != NRC_WIDE_WIDTH)
-            throw ApiError(NRC_ERR_UNSUPPORTED, "FP8 inference is implemented for the width-128 network only");
+        if (c.infer_precision == NRC_PRECISION_FP8 && c.width == NRC_WIDTH &&
+            (encoding != NRC_ENCODING_FREQUENCY || c.query_layout == NRC_QUERY_PADDED))
+            throw ApiError(NRC_ERR_UNSUPPORTED,
+                           std::string("FP8 inference at width 64 is implemented for InputEncoding::Frequency with compact "
+                                       "queries; requested: ") +
+                               (encoding == NRC_ENCODING_HASH ? "Hash" : encoding == NRC_ENCODING_FREQUENCY_SH ? "FrequencySH" : "Frequency") +
+                               (c.query_layout == NRC_QUERY_PADDED ? " with NRC_QUERY_PADDED" : ""));
         if (c.width == NRC_WIDE_WIDTH && encoding == NRC_ENCODING_HASH)
             throw ApiError(NRC_ERR_UNSUPPORTED, "the width-128 network supports the Frequency / FrequencySH encodings");
         if (c.query_layout != NRC_QUERY_COMPACT && c.query_layout != NRC_QUERY_PADDED)
@@ -1181,6 +1204,10 @@ nrc_status nrc_init(nrc_net* net, hipStream_t stream, int encoding, const nrc_co
         HIP_CHECK(hipMemset(net->wf_train, 0, sizeof(_Float16) * kFwdHalves));
         HIP_CHECK(hipMemset(net->wb_train, 0, sizeof(_Float16) * kWbHalves));
         HIP_CHECK(hipMemset(net->wf_infer, 0, sizeof(_Float16) * kFwdHalves));
+        if (net->fp8_64()) {
+            HIP_CHECK(hipMalloc(&net->img8, kInfer8Bytes));
+            HIP_CHECK(hipMemset(net->img8, 127, kInfer8Bytes));  // scale bytes the pack never writes: 2^0
+        }
         std::vector<int> fwd, bwd;
         build_scatter_maps(fwd, bwd, net->encoding);
         net->t16 = want_t16(net->encoding);
@@ -1301,6 +1328,9 @@ nrc_status nrc_infer_accumulate(nrc_net* net, const float* in, float* out, uint3
         else if (net->encoding == NRC_ENCODING_FREQUENCY_SH)
             HIP_CHECK(launch_infer_sh(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr), rgba, num_pixels,
                                       mode, w, net->stream));
+        else if (net->fp8_64())
+            HIP_CHECK(launch_infer8(0, in, out, n, net->wf_infer, net->img8, reinterpret_cast<const float*>(thr), rgba,
+                                    num_pixels, mode, w, net->stream));
         else
             HIP_CHECK(launch_infer_accumulate(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr), rgba,
                                               num_pixels, mode, w, net->stream, net->padq()));
@@ -1478,6 +1508,7 @@ void do_peer_step(nrc_net* net, const float* in, const float* tgt, uint32_t b_lo
                                          net->stream, kPxApplyOnly, polls));
         net->step = st;
         net->px_pending = false;
+        pack_fp8_64(net, net->stream);
     } else {
         const uint32_t seq = px_next(net->px_seq);
         if (form >= 0) {
@@ -1508,8 +1539,12 @@ void do_peer_step(nrc_net* net, const float* in, const float* tgt, uint32_t b_lo
                                         net->optim(st), net->stream, polls));
         }
         net->px_seq = seq;
-        if (form == kPxPushOnly) net->px_pending = true;
-        else net->step = st;
+        if (form == kPxPushOnly) {
+            net->px_pending = true;
+        } else {
+            net->step = st;
+            pack_fp8_64(net, net->stream);
+        }
     }
     if (loss_h) {
         if (loss_d) {
@@ -1609,6 +1644,7 @@ void do_train_apply(nrc_net* net, const float* grad_d, float* loss_h, float* los
     } else {
         HIP_CHECK(launch_reduce_adam(kApplyOnly, nullptr, 0, nullptr, const_cast<float*>(grad_d), ld, net->buffers(),
                                      net->optim(net->step), net->stream));
+        pack_fp8_64(net, net->stream);
         if (net->hash()) {
             GridBuffers gb = net->grid_buffers();
             gb.grad32 = grad_d + net->n_mlp;  // read-only in kApplyOnly
@@ -2006,6 +2042,23 @@ nrc_status nrc_debug_infer_precision(nrc_net* net, int precision, const float* i
             } else {
                 HIP_CHECK(launch_infer_tcnn(in, out, n, net->wf_infer, net->infer, stream));
             }
+            return;
+        }
+        if (net->fp8_64()) {
+            // a width-64 handle configured with FP8 keeps its f16 image: F16 = the production f16 kernel, FP8 = the FP8
+            // kernel (bits 4+: 1 = its A/B loser shape, debug library), for the in-process A/B
+            const int prec = precision & 15, variant = precision >> 4;
+            if ((prec != NRC_PRECISION_F16 && prec != NRC_PRECISION_FP8) || variant < 0 || variant > 1 ||
+                (variant && prec != NRC_PRECISION_FP8))
+                throw ApiError(NRC_ERR_INVALID_ARGUMENT, "unknown precision");
+            if (n == 0) return;
+            if (!in || !out) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "null input/output pointer");
+            const hipError_t e =
+                prec == NRC_PRECISION_F16
+                    ? launch_infer(in, out, n, net->wf_infer, stream, net->work_queue, &net->pool_parity, false)
+                    : launch_infer8(variant, in, out, n, net->wf_infer, net->img8, nullptr, nullptr, 0, -1, 1.0f, stream);
+            if (e == hipErrorNotSupported) throw ApiError(NRC_ERR_UNSUPPORTED, kDebugOnly);
+            HIP_CHECK(e);
             return;
         }
         if (!net->wide()) throw ApiError(NRC_ERR_UNSUPPORTED, "precision selection is for the width-128 network");

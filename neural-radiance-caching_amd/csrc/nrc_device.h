@@ -205,4 +205,79 @@ __device__ __forceinline__ void adam_pack_pre(int p, float gsum, const AdamIn& i
     if (in.bp >= 0) mb.wb_train[in.bp] = (_Float16)w;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Encoder v3 (round 2): fewer VALU for the same 40 K slots per lane half (slot map unchanged, slot_feature()).
+//
+// TriangleWave by the tent map. With x_k = 2 frac(2^k u) - 1, tri_k = |x_k| and x_{k+1} = 2 |x_k| - 1 (doubling a
+// point of the period-1 triangle wave folds it: frac(2^(k+1) u) = 2 frac(2^k u) - [frac(2^k u) >= 1/2]), so each
+// further octave is ONE v_fma_f32 with an |.| input modifier, and |x_k| is the cvt's input modifier: 1.5 VALU per
+// feature instead of 2.5 (fract, subtract, half a cvt). x_0 = 2 frac(|u|) - 1 (the wave is even). Rounding: 2|x| - 1
+// is exact unless |x| < 1/4, where it rounds by <= 2^-25; the doubling carries an error e to 2e, so after the five
+// steps of a lane half the features are within 2^-19 (1.9e-6) absolute of the directly evaluated wave.
+//
+// OneBlob with the wrap folded into two clamps. The closed form of blob_fast puts the masses A, B - A, 1 - B of the
+// intervals j0 = floor(4x) - 1 .. j0 + 2 into bins (j0 + i) & 3; tcnn's formula sends an interval outside
+// [-4, 7] to bin 3 instead. For t = 4x clamped to [-5, 8] that is exactly: A -> 0 when t < -4, A -> 1 when t >= 8,
+// B -> 1 when t >= 7 (every other out-of-range case is equivalent to one of these at the clamp ends), i.e. a med3 of
+// A and a max of B against step functions of t; the masses are rotated into place as before. The reference feeds
+// raw angles (theta in [0, pi], phi in (-pi, pi]) to OneBlob, so Cornell waves always take the wrap: this replaces
+// blob_many's wave-uniform branch (~25 extra VALU per input on the wrap side) by ~6 VALU per input on one path.
+// ------------------------------------------------------------------------------------------------
+// PADQ (padded RadianceQuery, nrc_config.query_layout): slot 33 of lane half 0 -- the first constant-one column,
+// canonical feature 66 -- carries the query's pad_ (Q.x3) instead: the reference's Identity(1) of pad_ (layout.h)
+template <bool PADQ = false>
+__device__ __forceinline__ void encode_v3(const QLane& Q, int h, h8 (&x)[5]) {
+    uint32_t w[20];
+    const float hs = h ? 64.0f : 1.0f;  // octaves 6..11 for the upper half
+    const float p[3] = {Q.p0 * hs, Q.p1 * hs, Q.p2 * hs};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        float g[6];
+        g[0] = fmaf(__builtin_amdgcn_fractf(__builtin_fabsf(p[d])), 2.0f, -1.0f);
+#pragma unroll
+        for (int k = 1; k < 6; ++k) g[k] = tent_step(g[k - 1]);
+#pragma unroll
+        for (int k = 0; k < 6; k += 2) w[(d * 6 + k) >> 1] = pk2_abs(g[k], g[k + 1]);
+    }
+    blob_v3(Q.b0, w[9], w[10]);
+    blob_v3(Q.b1, w[11], w[12]);
+    blob_v3(Q.b2, w[13], w[14]);
+    w[15] = pk2(Q.i0, Q.i1);
+    w[16] = pk2(Q.i2, PADQ && h == 0 ? Q.x3 : 1.0f);
+    w[17] = w[18] = w[19] = 0x3C003C00u;  // pad features = 1.0
+#pragma unroll
+    for (int kk = 0; kk < 5; ++kk) {
+        typedef uint32_t w4 __attribute__((ext_vector_type(4)));
+        w4 t4 = {w[4 * kk], w[4 * kk + 1], w[4 * kk + 2], w[4 * kk + 3]};
+        x[kk] = __builtin_bit_cast(h8, t4);
+    }
+}
+
+// ---- FP8 (OCP e4m3fn) pieces of the MX-MFMA inference kernels (width 128: nrc_kernels.hip; width 64: nrc_infer8.hip)
+typedef int i8v __attribute__((ext_vector_type(8)));  // 32 e4m3 bytes: one operand of the 32x32x64 MX MFMA
+
+template <int OPSEL>
+__device__ __forceinline__ f16v mfma_fp8(const i8v& a, const i8v& b, const f16v& c, uint32_t scale_a) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, OPSEL, (int)scale_a, 0, 127);
+}
+
+// MODE.FP16_OVFL (bit 23): overflowing f16 / FP8 results clamp to the largest finite value instead of inf / NaN
+__device__ __forceinline__ void fp8_saturating_converts() {
+    __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1 /* hwreg(HW_REG_MODE, 23, 1) */, 1u);
+}
+// two e4m3 bytes into word half `hi` of `old` (scale 1), saturating under fp8_saturating_converts()
+template <bool HI>
+__device__ __forceinline__ uint32_t cvt_sat_fp8(float a, float b, uint32_t old) {
+    typedef short s2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(s2, old), a, b,
+                                                                                  1.0f, HI));
+}
+
+// Zero every e4m3 byte of w whose sign bit is set (a negative value or -0): v_perm_b32's selectors 8..11 replicate the
+// sign bits of bytes 1, 3 of its second source and bytes 1, 3 of its first, so (w << 8, w) with 0x090B080A gives 0xFF
+// for each such byte.
+__device__ __forceinline__ uint32_t relu_e4m3x4(uint32_t w, uint32_t sh) {
+    return w & ~__builtin_amdgcn_perm(sh, w, 0x090B080Au);
+}
+
 }  // namespace nrc_amd

@@ -234,6 +234,26 @@ hipError_t launch_wide_adam(int mode, const float* slabs, int nchunks, const flo
 // diagnostic: e4m3 conversion exactly as the FP8 kernels do it (clamp to [lo, 448], v_cvt_pk_fp8_f32)
 hipError_t launch_fp8_convert(const float* x, uint8_t* y, int64_t n, int relu, hipStream_t s);
 
+// ---- FP8 inference of the 64-wide Frequency network (nrc_infer8.hip, DESIGN.md §12 "width 64"). Device image: 9 FP8
+// fragments of 2 KiB (L1..L4 x 2 M-blocks, then L5; each two 1-KiB planes as the width-128 FP8 fragments), then the
+// per-row E8M0 scale words [5 layers][32 lanes] (byte mb = row 32 mb + lane; unused bytes 127). Layer 0 is read from
+// the handle's f16 inference image.
+constexpr int kInfer8ImgBytes = 9 * 2048;
+constexpr int kInfer8Bytes = kInfer8ImgBytes + 5 * 32 * 4;
+__host__ __device__ constexpr int infer8_frag(int layer, int mb) { return layer <= 4 ? (layer - 1) * 2 + mb : 8; }
+// Byte j (0..31) of lane half h of a layer's FP8 B operand = register j & 15 of the previous layer's accumulator
+// block j >> 4: the previous layer's output row it carries (and the weight column stored at byte j of A-lane (r, h)).
+__host__ __device__ constexpr int f8_row64(int h, int j) {
+    return 32 * (j >> 4) + 8 * ((j & 15) >> 2) + 4 * h + (j & 3);
+}
+// the FP8 image + scales from the f32 inference weights (no host synchronisation: legal in a captured graph)
+hipError_t launch_pack8(const float* w_infer, uint8_t* img8, hipStream_t s);
+// wf: the f16 inference image (layer 0); mode -1 plain, 0 / 2 fused accumulation for queries [0, n_acc);
+// variant 0 = the product shape, 1 = the A/B loser (debug library, plain output only; else hipErrorNotSupported)
+hipError_t launch_infer8(int variant, const float* queries, float* out, int64_t n, const _Float16* wf,
+                         const uint8_t* img8, const float* thr, float* rgba, int64_t n_acc, int mode, float w,
+                         hipStream_t s);
+
 // ---- kernel launchers (nrc_kernels.hip). All are stream-ordered and capture-safe.
 // pools / parity: the handle's work-pool counters (kInferPoolBytes, zeroed at allocation) and its launch parity, which
 // the pooled variants flip (see ABL & 16384 in nrc_kernels.hip); variants that do not pool ignore both

@@ -162,7 +162,8 @@ class Network:
 
     def infer_precision(self, precision: int, inputs, outputs, numInputs: int, stream=None) -> None:
         """Width-128 network: inference through the f16 (0) or FP8 (1) weight image, whatever infer_precision the
-        handle was configured with (A/B timing, parity tests)."""
+        handle was configured with (A/B timing, parity tests). A width-64 handle configured with PRECISION_FP8 accepts
+        both too (its f16 image is always there)."""
         n = int(numInputs)
         pi = _dev_ptr(inputs, "inputs", n * self.query_dims if hasattr(inputs, "numel") else None)
         po = _dev_ptr(outputs, "outputs", n * 3 if hasattr(outputs, "numel") else None)
@@ -382,7 +383,8 @@ def encode(inputs, encoded, n: int, stream=None) -> None:
 def default_config(encoding: InputEncoding = InputEncoding.Frequency, width: int = 64,
                    infer_precision: int = 0) -> NrcConfig:
     """The reference's hyper-parameters for an encoding; width 128 selects the BASELINE configs[4] network (f16
-    training and inference), infer_precision PRECISION_FP8 its FP8 inference path (training stays f16);
+    training and inference), infer_precision PRECISION_FP8 the FP8 inference path (training stays f16) of the width-128
+    network or of the 64-wide one (width 64: Frequency encoding, compact queries);
     PRECISION_F16_ACC16 selects tiny-cuda-nn's f16-accumulate numerics for infer() (width 64, Frequency)."""
     c = lib().nrc_default_config(int(encoding))
     c.width = int(width)
