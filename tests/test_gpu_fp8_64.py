@@ -2,7 +2,20 @@
 float64 numpy model of its contract: layer 0 f16 x f16; ReLU outputs of layers 0..4 clamped to [0, 448] and rounded (RNE)
 onto e4m3; W1..W5 e4m3 with one power-of-two scale per row; f32 pre-activations; output through f16. Single-term weights:
 bitwise. Dense weights: the MX MFMA's block sum is not f32-exact (<= 2.2e-5 sum|a b|), so a pre-activation near an e4m3
-boundary can land one step away: rel-L2(GPU, model) <= B = 1.5 x the first GPU measurement (ceiling 6e-2)."""
+boundary can land one step away: rel-L2(GPU, model) <= B = 1.5 x the first GPU measurement (ceiling 6e-2).
+
+Also pinned, all bitwise:
+- the persistent loop's steady state (test_persistent_loop_*): 786,469 queries, at least two tile groups per wave at the
+  highest residency a CU allows, as a small base block tiled to that size -- against the model (single-term weights) and
+  against the base block's own launch (dense weights);
+- the fused accumulate epilogue (test_infer_accumulate_fp8_bitwise): RenderMode Full and CacheOnly, tiles that straddle
+  n_acc, n_acc = 0 and n_acc = n, and inside the steady-state loop, against infer + accumulate_render_radiance;
+- pack8_kernel's row rules (test_pack_row_rules_bitwise), observed through single-term dot products: the row exponent
+  at amax = 448 x 2^k and one float above, RNE ties, e4m3 subnormals and underflow of weights small beside their row's
+  maximum, the sign, the clamp of the exponent to the E8M0 range, in W1..W4 and in W5;
+- the debug library's two-tiles-per-wave shape against the product shape (test_two_tile_variant_bitwise), an odd tile
+  count included; the product library's refusal of it;
+- non-finite queries stay in their own columns; the per-call stream of infer()."""
 import numpy as np
 import pytest
 
@@ -199,3 +212,215 @@ def test_refusals(nrc, dev, encoding, padded):
     with pytest.raises(nrc.NrcError, match="FP8 inference at width 64"):
         net.init(stream=torch.cuda.current_stream(), encoding=enc, config=cfg)
     net.destroy()
+
+# ---- the persistent loop's steady state: a launch larger than every wave's first tile group
+N_BIG, N_BASE = 3 * 2 ** 18 + 37, 4099  # the base block is odd: no two tiles of the tiled launch hold the same rows
+_SHARED = {}
+
+def big_n(dev):
+    """N_BIG, or more where it takes more for two tile groups per wave: a CU holds 2048 threads, i.e. at most two
+    1024-thread blocks of 16 waves, and launch8 starts no more than CUs x resident blocks"""
+    import torch
+    waves = 2 * 16 * torch.cuda.get_device_properties(dev).multi_processor_count
+    n = N_BIG
+    while -(-n // 32) <= 2 * waves:
+        n += 2 ** 18
+    assert -(-n // 32) > 2 * waves
+    return n
+
+def tiled(a, n):
+    return a[np.arange(n) % len(a)]
+
+def rows_vary(y):  # a tile's rows are not its neighbours': a wrong tile index cannot pass
+    return np.mean((y[:-32] != y[32:]).any(axis=1)) >= 0.9
+
+def loop_single_path(orc):
+    """(base queries, params, model outputs): single_path_params with the W5 tap set whose outputs vary most"""
+    if "single" not in _SHARED:
+        q, p, best = exact_queries(N_BASE, 91), single_path_params(), None
+        for j in range(22):
+            w5 = np.zeros((16, 64), np.float32)
+            w5[np.arange(3), (3 * j + np.arange(3)) % 64] = [1.0, 0.5, 2.0]
+            p[OFFS[5]:] = w5.ravel()
+            want = model(orc, p, q)
+            distinct = len(np.unique(want, axis=0))
+            if np.mean(want != 0.0) >= 1.0 / 3.0 and (best is None or distinct > best[0]):
+                best = (distinct, p.copy(), want)
+        _SHARED["single"] = (q, best[1], best[2])
+    return _SHARED["single"]
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_persistent_loop_single_path_bitwise(nrc, orc, dev, net8, offset):
+    n = big_n(dev)
+    q, p, want = loop_single_path(orc)
+    assert np.mean(want != 0.0) >= 1.0 / 3.0 and rows_vary(want), "vacuous model outputs"
+    net8.set_state(nrc.StateSlot.INFER, p)
+    np.testing.assert_array_equal(run(net8, dev, tiled(q, n), offset=offset), tiled(want, n))
+
+def test_persistent_loop_dense_chunk_independence(nrc, dev, net8):
+    """Each query is its own MFMA column: the large launch is the base block's own launch (bounded by B against the
+    model in test_dense_weights), tiled"""
+    n = big_n(dev)
+    net8.set_state(nrc.StateSlot.INFER, dense_params(12))
+    q = nrc.synthetic.cornell_queries(N_BASE, seed=77)
+    base = run(net8, dev, q)
+    assert rows_vary(base), "vacuous outputs"
+    np.testing.assert_array_equal(run(net8, dev, tiled(q, n)), tiled(base, n))
+
+@pytest.mark.parametrize("mode", [0, 2])
+@pytest.mark.parametrize("n,n_acc", [(100_003, 90_001), (4096, 4096), (777, 0), (33, 1), (N_BIG, 700_001)])
+def test_infer_accumulate_fp8_bitwise(nrc, dev, net8, mode, n, n_acc):
+    """Fused epilogue of the FP8 kernel == its infer + nrc_accumulate_render_radiance, bit for bit (w = 1/6); render
+    radiance is not written, train-suffix radiance is, the frame buffer past n_acc is left alone. The last case runs
+    the epilogue's prefetched operands inside the steady-state loop."""
+    import torch
+    F = nrc.frame
+    net8.set_state(nrc.StateSlot.INFER, dense_params(15))
+    if n == N_BIG:
+        n = big_n(dev)
+        q = tiled(nrc.synthetic.cornell_queries(N_BASE, seed=78), n)
+    else:
+        q = nrc.synthetic.cornell_queries(n, seed=n)
+    q = _t(q, dev)
+    rng = np.random.default_rng(n_acc)
+    thr = _t(rng.uniform(0, 1, (max(n_acc, 1), 3)).astype(np.float32), dev)
+    rgba0 = _t(rng.uniform(0, 1, (n_acc + 8, 4)).astype(np.float32), dev)
+    ref_res = torch.empty((n, 3), device=dev)
+    net8.infer(q, ref_res, n)
+    ref_rgba = rgba0.clone()
+    F.accumulate_render_radiance(ref_res, thr, ref_rgba, n_acc, mode, 5)
+    res = torch.full((n, 3), -3.0, device=dev)
+    rgba = rgba0.clone()
+    F.infer_accumulate(net8, q, res, n, thr, rgba, n_acc, mode, 5)
+    torch.cuda.synchronize()
+    assert float(ref_res.abs().sum()) > 0.0
+    assert n_acc == 0 or not torch.equal(ref_rgba[:n_acc, :3], rgba0[:n_acc, :3]), "vacuous accumulation"
+    assert torch.equal(rgba, ref_rgba)
+    assert torch.equal(rgba[n_acc:], rgba0[n_acc:])
+    assert torch.equal(res[n_acc:], ref_res[n_acc:])
+    assert torch.all(res[:n_acc] == -3.0)
+    with pytest.raises(nrc.NrcError):
+        F.infer_accumulate(net8, q, res, n, thr, rgba, n_acc, F.RenderMode.DebugThroughputOnly, 0)
+
+# ---- pack8_kernel's row rules. The pack image cannot be read back: a row under test has weight v on a live unit (a
+# constant-one feature times a power of two, act) and weight M on a dead unit (an empty OneBlob bin: exactly +0), so M
+# sets the row exponent and the dot product keeps one term; identity weights carry act x quantised(v) to the output.
+def probe_params(layer, rows):
+    """rows: three (v, M, act), or (v, None, act) for v in every column; chain c lives on unit u[c] of every layer"""
+    u, d = (layer, 29 + layer, 58 + layer), 40 + layer
+    p = np.zeros(OFFS[-1], np.float32)
+    w0 = np.zeros((64, 80), np.float32)
+    w0[u, 66 + np.arange(3)] = [act for _, _, act in rows]
+    w0[d, 36] = 1.0
+    p[:OFFS[1]] = w0.ravel()
+    for l in range(1, 6):
+        w = np.zeros(SHAPES[l], np.float32)
+        for c, (v, M, _) in enumerate(rows):
+            r = c if l == 5 else u[c]
+            if l != layer:
+                w[r, u[c]] = 1.0
+            elif M is None:
+                w[r] = v
+            else:
+                w[r, u[c]], w[r, d] = v, M
+        p[OFFS[l]:OFFS[l + 1]] = w.ravel()
+    return p
+
+def pack_cases():
+    """(group, v, M, act, expected output), worked by hand: e = the row exponent of M, the output act x RNE_e4m3(v /
+    2^e) x 2^e. act keeps that value a normal e4m3 number, so the later layers and the f16 output pass it on exactly."""
+    f32, up = np.float32, lambda x: np.nextafter(np.float32(x), np.float32(np.inf))  # noqa: E731
+    cases = []
+    for k, act in ((-3, 256.0), (0, 64.0), (2, 64.0)):
+        s, m = 2.0 ** k, f32(448.0 * 2.0 ** k)
+        # amax = 448 x 2^k: e = k; one float above: e = k + 1. Normal e4m3 numbers scale with e: 17 -> 16, 8.5 -> 8 (ties
+        # to even), the same value. The two exponents differ only below 2^-6: 3 x 2^-9 is an exact subnormal under
+        # e = k, and the tie 1.5 x 2^-9 -> 2 x 2^-9 under e = k + 1
+        cases += [("boundary", 17.0 * s, m, 1.0, 16.0 * s), ("boundary", 17.0 * s, up(m), 1.0, 16.0 * s),
+                  ("boundary", 3.0 * s / 512.0, m, act, act * 3.0 * s / 512.0),
+                  ("boundary", 3.0 * s / 512.0, up(m), act, act * 4.0 * s / 512.0)]
+    cases += [("tie", 17.0, 448.0, 1.0, 16.0), ("tie", 19.0, 448.0, 1.0, 20.0), ("tie", up(17.0), 448.0, 1.0, 18.0)]
+    cases += [("subnormal", k / 512.0, 448.0, 64.0, k / 8.0) for k in range(1, 8)]
+    cases += [("subnormal", 1.5 / 512.0, 448.0, 64.0, 0.25), ("subnormal", 2.5 / 512.0, 448.0, 64.0, 0.25),
+              ("subnormal", 0.5 / 512.0, 448.0, 64.0, 0.0), ("subnormal", 0.75 / 512.0, 448.0, 64.0, 0.125),
+              ("subnormal", 2.0 ** -11, 448.0, 64.0, 0.0)]
+    cases += [("sign", -v, M, act, 0.0) for g, v, M, act, _ in cases]
+    # e clamps to -127 (1e-40 is an f32 denormal: frexp gives e = -141); 3e38 = 0.88 x 2^128: e = 120, under which 1 is
+    # flushed and 2^114 = 2^-6 x 2^120 is the smallest normal (the pre-activation 2^114 saturates at 448)
+    cases += [("clamp", 1e-40, None, 1.0, 0.0), ("clamp", 1.0, 3e38, 1.0, 0.0), ("clamp", 2.0 ** 114, 3e38, 1.0, 448.0)]
+    return cases
+
+@pytest.mark.parametrize("layer", [1, 2, 3, 4, 5])
+def test_pack_row_rules_bitwise(nrc, orc, dev, net8, layer):
+    """layer 5: W5, whose fragment uses scale byte 0 only; its three rows carry three different exponents at once. W5's
+    output is not clamped, so 2^114 (inf in f16) is left to the hidden layers. Rows 3..31 of W5's fragment reach no
+    output and cannot be observed."""
+    cases = [c for c in pack_cases() if layer < 5 or c[4] <= 448.0 and c[1] < 2.0 ** 100]
+    cases += [("fill", 1.0, 448.0, 1.0, 1.0)] * (-len(cases) % 3)
+    q = exact_queries(5, 17)
+    for i in range(0, len(cases), 3):
+        trio = cases[i:i + 3]
+        p = probe_params(layer, [(v, M, act) for _, v, M, act, _ in trio])
+        net8.set_state(nrc.StateSlot.INFER, p)
+        got, want = run(net8, dev, q), model(orc, p, q)
+        hand = np.tile(np.float32([c[4] for c in trio]), (len(q), 1))
+        np.testing.assert_array_equal(want, hand, err_msg=f"the probe does not carry {trio} to the output")
+        assert np.isfinite(got).all(), trio
+        np.testing.assert_array_equal(got, want, err_msg=f"layer {layer}: {trio}")
+    for group in ("boundary", "tie", "subnormal"):
+        assert any(c[0] == group and c[4] != 0.0 for c in cases), group
+
+# ---- the debug library's two-tiles-per-wave shape (launch8<-1, 2, 512>)
+def test_two_tile_variant_bitwise(nrc, dev, net8):
+    """Two tiles per wave iteration == the product shape, bit for bit; with an odd tile count (n = 1, 33, 65, 4097) the
+    second tile of the last group lies wholly past n. Debug library only (tests/test_gpu_debug_lib.py runs it there)."""
+    if not nrc._lib.is_debug_library():
+        pytest.skip("A/B variant of the debug library (libnrc_amd_debug.so)")
+    net8.set_state(nrc.StateSlot.INFER, dense_params(16))
+    base = nrc.synthetic.cornell_queries(N_BASE, seed=79)
+    for n in (1, 33, 65, 4097, big_n(dev)):
+        q = tiled(base, n)
+        one = run(net8, dev, q, precision=nrc._lib.PRECISION_FP8)
+        assert n < 33 or rows_vary(one), "vacuous outputs"
+        np.testing.assert_array_equal(run(net8, dev, q, precision=nrc._lib.PRECISION_FP8 | (1 << 4)), one, err_msg=str(n))
+
+def test_two_tile_variant_refused_by_product_library(nrc, dev, net8):
+    if nrc._lib.is_debug_library():
+        return
+    with pytest.raises(nrc.NrcError, match="debug library"):
+        run(net8, dev, nrc.synthetic.cornell_queries(33, seed=80), precision=nrc._lib.PRECISION_FP8 | (1 << 4))
+
+# ---- small things
+def test_non_finite_queries_stay_in_their_columns(nrc, dev, net8):
+    net8.set_state(nrc.StateSlot.INFER, dense_params(17))
+    q = nrc.synthetic.cornell_queries(33, seed=81)
+    bad = q.copy()
+    bad[5] = np.nan
+    bad[20, 1] = np.inf
+    keep = np.setdiff1d(np.arange(33), [5, 20])
+    np.testing.assert_array_equal(run(net8, dev, bad)[keep], run(net8, dev, q)[keep])
+
+def test_infer_on_a_side_stream(nrc, dev, net8):
+    """infer(stream=) (nrc_infer_stream) after a train on the handle's own stream: the training step's weights and its
+    FP8 repack are ordered before the side stream's launch by an event, nothing else"""
+    import torch
+    net8.set_state(nrc.StateSlot.PARAMS, dense_params(18, 1.2))
+    bq, bt = nrc.synthetic.cornell_batch(nrc.BATCH_SIZE, seed=33)
+    bq, bt = _t(bq, dev), _t(bt, dev)
+    n = 4097
+    q = _t(nrc.synthetic.cornell_queries(n, seed=82), dev)
+    out, ref = torch.full((n + 8, 3), 777.0, device=dev), torch.empty((n, 3), device=dev)
+    main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+    before = net8.get_state(nrc.StateSlot.INFER)
+    net8.train(bq, bt)
+    done = torch.cuda.Event()
+    done.record(main)
+    side.wait_event(done)
+    net8.infer(q, out, n, stream=side)
+    side.synchronize()
+    net8.setStream(main)
+    net8.infer(q, ref, n)
+    torch.cuda.synchronize()
+    assert not np.array_equal(before, net8.get_state(nrc.StateSlot.INFER)), "the step changed nothing"
+    assert torch.equal(out[:n], ref) and torch.all(out[n:] == 777.0)
+    assert float(ref.abs().sum()) > 0.0
