@@ -72,6 +72,26 @@ nrc_status nrc_infer_accumulate(nrc_net* net, const float* queries_d, float* res
                                 const nrc_float3* end_render_throughput_d, float* output_rgba_d, uint32_t num_pixels,
                                 int mode, uint32_t iteration_index);
 
+/* nrc_infer_accumulate that skips the network for render queries whose result the epilogue provably discards. Same
+ * arguments, argument checks, modes (Full, CacheOnly), stream and weights.
+ * Liveness: a render query i < num_pixels is dead iff T.x == 0 && T.y == 0 && T.z == 0 under IEEE compares
+ * (T = end_render_throughput_d[i]; +-0 is dead, a NaN component is live). Every other render query and every query in
+ * [num_pixels, n) is live.
+ * Live queries: exactly nrc_infer_accumulate's results, bit for bit -- frame-buffer pixels by the same float operations,
+ * train-suffix radiance into results_d[num_pixels, n).
+ * Dead pixels receive what the dense epilogue computes with radiance +0: Full dst.c = fmaf(T.c * 0.0f, w, dst.c),
+ * CacheOnly dst.c = 0.0f * T.c, dst.w = 1 in both. That equals nrc_infer_accumulate bitwise whenever the dense radiance
+ * of the pixel is finite (the -0 / +0 sign cases included). The one deviation: where the dense radiance is inf (f16
+ * overflow of the output), the dense path writes NaN (inf * 0) and this one does not.
+ * results_d[0, num_pixels) is never written, the throughput is read in [0, num_pixels) only, nothing is read or written
+ * past n. Handles: width 64, NRC_ENCODING_FREQUENCY, NRC_PRECISION_F16, compact queries; every other handle (FP8 at
+ * width 64, NRC_PRECISION_F16_ACC16, Hash, FrequencySH, width 128, padded queries) is NRC_ERR_UNSUPPORTED with a message
+ * that names the combination. nrc_process_frame / nrc_process_frame_shard take this entry for their fused Full /
+ * CacheOnly inference when the process-wide knob "frame_sparse" is 1 and the handle is supported (nrc_c.h). */
+nrc_status nrc_infer_accumulate_sparse(nrc_net* net, const float* queries_d, float* results_d, uint32_t n,
+                                       const nrc_float3* end_render_throughput_d, float* output_rgba_d,
+                                       uint32_t num_pixels, int mode, uint32_t iteration_index);
+
 /* copy_radiance_to_output_buffer (nrc_helpers.cu:54-73): out = (radiance, 1) for n pixels. */
 nrc_status nrc_copy_radiance_to_output(const nrc_float3* radiance_d, float* output_rgba_d, uint32_t num_pixels,
                                        hipStream_t stream);

@@ -264,12 +264,13 @@ bool want_t16(int encoding) {
     return encoding == NRC_ENCODING_FREQUENCY || encoding == NRC_ENCODING_HASH;
 }
 
-std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 const char* const kKnobNames[kKnobCount] = {"train_kernel", "train_shape", "scatter_min", "scatter_max", "dc_dw0_delay",
                                             "hash_infer", "hash_feat_abl", "t16_groups", "hash_feat_p", "peer_path",
                                             "px_polls", "scatter_part", "scatter_compact", "hash_train_feat",
-                                            "hash_adam", "train_fused", "fuse_mode", "tcnn_reentry", "train_prio"};
-static_assert(kKnobCount == 19, "one initial value and one name per knob");
+                                            "hash_adam", "train_fused", "fuse_mode", "tcnn_reentry", "train_prio",
+                                            "frame_sparse"};
+static_assert(kKnobCount == 20, "one initial value and one name per knob");
 
 std::string config_json(int encoding, const nrc_config& c) {
     char buf[2048];
@@ -982,6 +983,24 @@ bool nrc_amd::net_infer_fusable(nrc_net* net) {
     return net->cfg.infer_precision != NRC_PRECISION_F16_ACC16;
 }
 
+// why nrc_infer_accumulate_sparse cannot serve the handle (names the combination), or null
+static const char* sparse_unsupported(nrc_net* net) {
+    if (net->wide()) return "sparse fused accumulation: width 128 is not supported (width 64 only)";
+    if (net->hash()) return "sparse fused accumulation: InputEncoding::Hash is not supported (Frequency only)";
+    if (net->encoding == NRC_ENCODING_FREQUENCY_SH)
+        return "sparse fused accumulation: InputEncoding::FrequencySH is not supported (Frequency only)";
+    if (net->cfg.infer_precision == NRC_PRECISION_F16_ACC16)
+        return "sparse fused accumulation: NRC_PRECISION_F16_ACC16 is not supported (F16 only)";
+    if (net->fp8_64()) return "sparse fused accumulation: FP8 at width 64 is not supported (F16 only)";
+    if (net->padq()) return "sparse fused accumulation: padded queries are not supported (compact only)";
+    return nullptr;
+}
+
+bool nrc_amd::net_infer_sparse_ok(nrc_net* net) {
+    check_live(net);
+    return sparse_unsupported(net) == nullptr;
+}
+
 void nrc_amd::net_check_protocol(nrc_net* net) {
     check_live(net);
     net->check_protocol();
@@ -1022,6 +1041,7 @@ bool knob_value_ok(Knob k, int v) {
         case kKnobFuseMode: return v >= -1 && v <= 4;
         case kKnobTcnnReentry: return v >= -1 && v <= 1;
         case kKnobTrainPrio: return v >= -1 && v <= 2;
+        case kKnobFrameSparse: return v >= -1 && v <= 1;
         default: return false;
     }
 }
@@ -1334,6 +1354,24 @@ nrc_status nrc_infer_accumulate(nrc_net* net, const float* in, float* out, uint3
         else
             HIP_CHECK(launch_infer_accumulate(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr), rgba,
                                               num_pixels, mode, w, net->stream, net->padq()));
+    });
+}
+
+nrc_status nrc_infer_accumulate_sparse(nrc_net* net, const float* in, float* out, uint32_t n, const nrc_float3* thr,
+                                       float* rgba, uint32_t num_pixels, int mode, uint32_t iteration_index) {
+    return guarded([&] {
+        check_live(net);
+        if (mode != NRC_RENDER_FULL && mode != NRC_RENDER_CACHE_ONLY)
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "fused accumulation supports RenderMode Full and CacheOnly only");
+        if (num_pixels > n) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "num_pixels > n");
+        if (const char* why = sparse_unsupported(net)) throw ApiError(NRC_ERR_UNSUPPORTED, why);
+        if (n == 0) return;
+        if (!in || (num_pixels < n && !out)) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "null query/result pointer");
+        if (num_pixels > 0 && (!thr || !rgba || (reinterpret_cast<uintptr_t>(rgba) & 15)))
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "throughput / 16-byte aligned float4 frame buffer required");
+        const float w = 1.0f / (float)(iteration_index + 1u);  // nrc_helpers.cu:98
+        HIP_CHECK(launch_infer_accumulate_sparse(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr), rgba,
+                                                 num_pixels, mode, w, net->stream));
     });
 }
 

@@ -228,13 +228,19 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
     // (a handle inferring with tcnn's f16 accumulation has no fused form: it takes infer + accumulate)
     const bool fuse = !skip_render && !p->keep_render_results && !rf && net_infer_fusable(net) &&
                       (mode == NRC_RENDER_FULL || mode == NRC_RENDER_CACHE_ONLY);
+    // knob "frame_sparse": zero-throughput pixels skip the MLP (nrc_infer_accumulate_sparse) on handles it supports
+    const bool sparse = fuse && knob(kKnobFrameSparse) == 1 && net_infer_sparse_ok(net);
     if ((uint64_t)screen + tiles > 0) require(qi && ri, "inference buffers are NULL");
     auto infer_range = [&](uint32_t first, uint32_t count, uint32_t acc_pixels) {
         // queries [first, first + count); the first acc_pixels of them are render queries of pixels first..
         if (count == 0) return;
         const float* q = qi + (size_t)first * QD;
         float* r = reinterpret_cast<float*>(ri + first);
-        if (fuse && acc_pixels > 0)
+        if (fuse && acc_pixels > 0 && sparse)
+            check(nrc_infer_accumulate_sparse(net, q, r, count, fb->last_render_throughput_d + first,
+                                              fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode,
+                                              p->iteration_index));
+        else if (fuse && acc_pixels > 0)
             check(nrc_infer_accumulate(net, q, r, count, fb->last_render_throughput_d + first,
                                        fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode, p->iteration_index));
         else

@@ -276,6 +276,12 @@ hipError_t read_infer_clock(uint64_t* host, int64_t cap_waves, int64_t* waves);
 // inference with accumulate_render_radiance fused for queries [0, n_acc) (mode 0 Full / 2 CacheOnly)
 hipError_t launch_infer_accumulate(const float* queries, float* out, int64_t n, const _Float16* wf, const float* thr,
                                    float* rgba, int64_t n_acc, int mode, float w, hipStream_t s, bool padq = false);
+// the same with the MLP skipped for render queries whose throughput is exactly zero (nrc_infer_sparse.hip): width 64,
+// Frequency, F16, compact queries; mode 0 Full / 2 CacheOnly. A block walks its index range in chunks of kSparseChunk.
+constexpr int kSparseChunk = 2048;
+hipError_t launch_infer_accumulate_sparse(const float* queries, float* out, int64_t n, const _Float16* wf,
+                                          const float* thr, float* rgba, int64_t n_acc, int mode, float w,
+                                          hipStream_t s);
 // InputEncoding::Hash inference (mode -1: plain; 0 / 2: fused accumulation for queries [0, n_acc))
 // feat: the handle's [NRC_HASH_LEVELS][kHashFeatStride] level-feature workspace (hash_feature_kernel, round 3), or
 // nullptr for the round-2 gather kernel (also knob "hash_infer" = 1)
@@ -425,7 +431,9 @@ enum Knob : int {
                               // MFMAs per block and chunk (round 6, first form), 1 (-1) four 4x4x4 identity MFMAs
     kKnobTrainPrio = 18,      // debug library, A/B: role-split training kernel with 1 the dW waves / 2 the chain waves
                               // at s_setprio 1 (-1 / 0: no priority)
-    kKnobCount = 19
+    kKnobFrameSparse = 19,    // nrc_process_frame / _shard: 1 = the fused Full / CacheOnly inference through
+                              // nrc_infer_accumulate_sparse on handles it supports (-1 / 0: the dense kernel)
+    kKnobCount = 20
 };
 int knob(Knob k);
 
@@ -557,6 +565,8 @@ void* net_frame_scratch(nrc_net* net, size_t bytes);
 bool net_padq(nrc_net* net);
 // inference can take the fused accumulation epilogue (not with NRC_PRECISION_F16_ACC16)
 bool net_infer_fusable(nrc_net* net);
+// nrc_infer_accumulate_sparse serves the handle (width 64, Frequency, F16, compact queries)
+bool net_infer_sparse_ok(nrc_net* net);
 // throws NRC_ERR_INTERNAL if a training kernel or a peer-exchange wait reported a timeout (after a stream sync)
 void net_check_protocol(nrc_net* net);
 // nrc_train_dp with the loss left in a device slot (frame driver)

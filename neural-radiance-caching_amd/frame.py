@@ -83,6 +83,7 @@ def _sigs():
         "nrc_accumulate_render_radiance": [vp, vp, vp, u32, ctypes.c_int, u32, vp],
         "nrc_copy_radiance_to_output": [vp, vp, u32, vp],
         "nrc_infer_accumulate": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
+        "nrc_infer_accumulate_sparse": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
         "nrc_propagate_train_radiance": [vp, vp, u32, vp, vp, u32, vp],
         "nrc_accumulate_render_radiance_factored": [vp, vp, vp, vp, u32, ctypes.c_int, u32, vp],
         "nrc_copy_radiance_to_output_factored": [vp, vp, vp, u32, vp],
@@ -155,6 +156,20 @@ def infer_accumulate(net, queries, results, n: int, throughput, output_rgba, num
     check(_sigs().nrc_infer_accumulate(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
                                        _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
                                        int(num_pixels), int(mode), int(iteration_index)))
+
+
+# indices per chunk of a block's range in the sparse kernel (kSparseChunk, csrc/nrc_internal.h)
+SPARSE_CHUNK = 2048
+
+
+def infer_accumulate_sparse(net, queries, results, n: int, throughput, output_rgba, num_pixels: int, mode: RenderMode,
+                            iteration_index: int) -> None:
+    """infer_accumulate() that skips the network for render queries whose throughput is exactly (0, 0, 0): their
+    pixels get the dense epilogue's value for radiance +0; live queries are bit-identical to infer_accumulate()
+    (frame.h). Width 64, Frequency, F16, compact queries; other handles raise NrcError (NRC_ERR_UNSUPPORTED)."""
+    check(_sigs().nrc_infer_accumulate_sparse(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
+                                              _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
+                                              int(num_pixels), int(mode), int(iteration_index)))
 
 
 def copy_radiance_to_output(radiance, output_rgba, num_pixels: int, stream=None) -> None:
