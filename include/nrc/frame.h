@@ -14,7 +14,9 @@
  *
  * Same conventions as nrc_c.h: plain device pointers, int status, stream-ordered, never throws.
  * Records are the reference's structs byte for byte (neural_radiance_caching.h:56-99); the reference
- * is built with USE_REFLECTANCE_FACTORING 0 (config.h:118), the only variant restated here.
+ * is built with USE_REFLECTANCE_FACTORING 0 (config.h:118). Its USE_REFLECTANCE_FACTORING 1 variant is restated by the
+ * *_factored entries below: as kernels of their own, and fused into the inference epilogue
+ * (nrc_infer_accumulate_factored; nrc_process_frame takes it under the knob "frame_factored_fused").
  */
 #ifndef NRC_FRAME_H
 #define NRC_FRAME_H
@@ -91,6 +93,28 @@ nrc_status nrc_infer_accumulate(nrc_net* net, const float* queries_d, float* res
 nrc_status nrc_infer_accumulate_sparse(nrc_net* net, const float* queries_d, float* results_d, uint32_t n,
                                        const nrc_float3* end_render_throughput_d, float* output_rgba_d,
                                        uint32_t num_pixels, int mode, uint32_t iteration_index);
+
+/* nrc_infer_accumulate for USE_REFLECTANCE_FACTORING 1: inference with nrc_accumulate_render_radiance_factored (below)
+ * fused into its epilogue. Arguments and argument checks of nrc_infer_accumulate, on the handle's stream with the
+ * inference (EMA) weights.
+ * Modes: Full, CacheOnly and DebugCacheNoThroughputModulation -- the last is the factored copy_radiance_to_output_buffer,
+ * out = (L * R, 1); end_render_throughput_d may then be NULL and is never read. Any other mode:
+ * NRC_ERR_INVALID_ARGUMENT.
+ * Contract: for the render queries [0, num_pixels) output_rgba_d receives, bit for bit, what nrc_infer_stream on the
+ * same handle followed by nrc_accumulate_render_radiance_factored writes: with L the inferred radiance, T the
+ * throughput, R = diffuse + specular of the query (floats 9..11 + 12..14) and w = 1 / (iteration_index + 1),
+ * Full dst.c = fmaf((T.c * L.c) * R.c, w, dst.c), CacheOnly dst.c = (L.c * T.c) * R.c, mode 4 dst.c = L.c * R.c, and
+ * dst.w = 1. (As in nrc_infer_accumulate the epilogue runs in the inference kernel's float mode, which flushes f32
+ * results below 2^-126 to zero.) R is taken from the registers that already hold the query for the encoder: no query
+ * record is read twice and no radiance round-trips through memory.
+ * results_d[0, num_pixels) is never written; queries [num_pixels, n) go to results_d exactly as nrc_infer writes them;
+ * nothing is read or written past n; num_pixels may be 0 or n.
+ * Handles: width 64, NRC_ENCODING_FREQUENCY, compact queries, infer_precision NRC_PRECISION_F16 or NRC_PRECISION_FP8.
+ * Every other handle (padded queries, Hash, FrequencySH, width 128, NRC_PRECISION_F16_ACC16) is NRC_ERR_UNSUPPORTED
+ * with a message that names the combination. */
+nrc_status nrc_infer_accumulate_factored(nrc_net* net, const float* queries_d, float* results_d, uint32_t n,
+                                         const nrc_float3* end_render_throughput_d, float* output_rgba_d,
+                                         uint32_t num_pixels, int mode, uint32_t iteration_index);
 
 /* copy_radiance_to_output_buffer (nrc_helpers.cu:54-73): out = (radiance, 1) for n pixels. */
 nrc_status nrc_copy_radiance_to_output(const nrc_float3* radiance_d, float* output_rgba_d, uint32_t num_pixels,
@@ -208,11 +232,19 @@ typedef struct nrc_frame_params {
     int32_t train;                /* 0: inference/accumulation only */
     int32_t keep_render_results;  /* 1: also write the render queries' radiance to results_inference (unfused
                                      infer + accumulate, e.g. for the reference's debug dump); 0: fused */
-    int32_t reflectance_factoring; /* 1: USE_REFLECTANCE_FACTORING 1 (the *_factored kernels above; unfused) */
+    int32_t reflectance_factoring; /* 1: USE_REFLECTANCE_FACTORING 1: infer + the *_factored kernels above; with the
+                                      knob "frame_factored_fused" = 1 and !keep_render_results, on handles
+                                      nrc_infer_accumulate_factored serves, the accumulation is fused into inference:
+                                      results_inference[0, screen) (CacheFirstVertex: results_cache_vis) is then not
+                                      written */
 } nrc_frame_params;
 
 /* Runs, on the handle's stream: infer -> accumulate (fused into infer for Full / CacheOnly unless
  * keep_render_results; cache-vis for CacheFirstVertex) -> [if records] propagate -> shuffle -> NUM_BATCHES x train.
+ * With reflectance_factoring the accumulation is a kernel of its own after inference, or, under the process-wide knob
+ * "frame_factored_fused" = 1 (nrc_c.h), the epilogue of nrc_infer_accumulate_factored: Full / CacheOnly over the render +
+ * tile launch (whole frame and shard range alike), CacheFirstVertex in mode 4 over the cache-vis queries. Factored
+ * propagation and everything after it are the same either way, and so is the frame buffer, bit for bit.
  * loss_h (optional) receives the mean of the NUM_BATCHES minibatch losses (Device.cpp:1503-1511) and makes the call
  * block once at the end (the reference blocks after every minibatch); 0 if the frame did not train. */
 nrc_status nrc_process_frame(nrc_net* net, const nrc_frame_buffers* buffers, const nrc_frame_params* params,

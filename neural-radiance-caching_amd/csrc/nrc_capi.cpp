@@ -264,13 +264,13 @@ bool want_t16(int encoding) {
     return encoding == NRC_ENCODING_FREQUENCY || encoding == NRC_ENCODING_HASH;
 }
 
-std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 const char* const kKnobNames[kKnobCount] = {"train_kernel", "train_shape", "scatter_min", "scatter_max", "dc_dw0_delay",
                                             "hash_infer", "hash_feat_abl", "t16_groups", "hash_feat_p", "peer_path",
                                             "px_polls", "scatter_part", "scatter_compact", "hash_train_feat",
                                             "hash_adam", "train_fused", "fuse_mode", "tcnn_reentry", "train_prio",
-                                            "frame_sparse"};
-static_assert(kKnobCount == 20, "one initial value and one name per knob");
+                                            "frame_sparse", "frame_factored_fused"};
+static_assert(kKnobCount == 21, "one initial value and one name per knob");
 
 std::string config_json(int encoding, const nrc_config& c) {
     char buf[2048];
@@ -1001,6 +1001,23 @@ bool nrc_amd::net_infer_sparse_ok(nrc_net* net) {
     return sparse_unsupported(net) == nullptr;
 }
 
+// why nrc_infer_accumulate_factored cannot serve the handle (names the combination), or null
+static const char* factored_unsupported(nrc_net* net) {
+    if (net->wide()) return "fused factored accumulation: width 128 is not supported (width 64 only)";
+    if (net->hash()) return "fused factored accumulation: InputEncoding::Hash is not supported (Frequency only)";
+    if (net->encoding == NRC_ENCODING_FREQUENCY_SH)
+        return "fused factored accumulation: InputEncoding::FrequencySH is not supported (Frequency only)";
+    if (net->cfg.infer_precision == NRC_PRECISION_F16_ACC16)
+        return "fused factored accumulation: NRC_PRECISION_F16_ACC16 is not supported (F16 and FP8 only)";
+    if (net->padq()) return "fused factored accumulation: padded queries are not supported (compact only)";
+    return nullptr;
+}
+
+bool nrc_amd::net_infer_factored_ok(nrc_net* net) {
+    check_live(net);
+    return factored_unsupported(net) == nullptr;
+}
+
 void nrc_amd::net_check_protocol(nrc_net* net) {
     check_live(net);
     net->check_protocol();
@@ -1042,6 +1059,7 @@ bool knob_value_ok(Knob k, int v) {
         case kKnobTcnnReentry: return v >= -1 && v <= 1;
         case kKnobTrainPrio: return v >= -1 && v <= 2;
         case kKnobFrameSparse: return v >= -1 && v <= 1;
+        case kKnobFrameFactoredFused: return v >= -1 && v <= 1;
         default: return false;
     }
 }
@@ -1372,6 +1390,30 @@ nrc_status nrc_infer_accumulate_sparse(nrc_net* net, const float* in, float* out
         const float w = 1.0f / (float)(iteration_index + 1u);  // nrc_helpers.cu:98
         HIP_CHECK(launch_infer_accumulate_sparse(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr), rgba,
                                                  num_pixels, mode, w, net->stream));
+    });
+}
+
+nrc_status nrc_infer_accumulate_factored(nrc_net* net, const float* in, float* out, uint32_t n, const nrc_float3* thr,
+                                         float* rgba, uint32_t num_pixels, int mode, uint32_t iteration_index) {
+    return guarded([&] {
+        check_live(net);
+        const bool copy = mode == NRC_RENDER_DEBUG_CACHE_NO_THROUGHPUT_MODULATION;  // reads no throughput
+        if (mode != NRC_RENDER_FULL && mode != NRC_RENDER_CACHE_ONLY && !copy)
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "fused factored accumulation supports RenderMode Full, CacheOnly and "
+                                                     "DebugCacheNoThroughputModulation only");
+        if (num_pixels > n) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "num_pixels > n");
+        if (const char* why = factored_unsupported(net)) throw ApiError(NRC_ERR_UNSUPPORTED, why);
+        if (n == 0) return;
+        if (!in || (num_pixels < n && !out)) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "null query/result pointer");
+        if (num_pixels > 0 && ((!copy && !thr) || !rgba || (reinterpret_cast<uintptr_t>(rgba) & 15)))
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "throughput / 16-byte aligned float4 frame buffer required");
+        const float w = 1.0f / (float)(iteration_index + 1u);  // nrc_helpers.cu:98
+        if (net->fp8_64())
+            HIP_CHECK(launch_infer8(0, in, out, n, net->wf_infer, net->img8, reinterpret_cast<const float*>(thr), rgba,
+                                    num_pixels, kInfer8Factored + mode, w, net->stream));
+        else
+            HIP_CHECK(launch_infer_accumulate_factored(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr),
+                                                       rgba, num_pixels, mode, w, net->stream));
     });
 }
 

@@ -253,6 +253,22 @@ __device__ __forceinline__ void encode_v3(const QLane& Q, int h, h8 (&x)[5]) {
     }
 }
 
+// Value of lane + 32 for the lanes of half 0 (v_permlane32_swap: the upper half of one operand trades places with the
+// lower half of the other; with the same register as both, the second result holds the upper half's value in half 0)
+__device__ __forceinline__ float upper_half(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    return __builtin_bit_cast(f2, __builtin_amdgcn_permlane32_swap(u, u, false, false))[1];
+}
+
+// RadianceQuery::reflectance() = diffuse + specular (neural_radiance_caching.h:118) of the tile's queries from the
+// registers that hold them: lane half 0 carries diffuse in QLane::i0..i2 (floats 9..11), half 1 specular (12..14).
+// Valid in lane half 0. One f32 add per component, operands in the order of reflectance() of nrc_frame.hip.
+__device__ __forceinline__ void reflectance_half0(const QLane& Q, float (&R)[3]) {
+    R[0] = Q.i0 + upper_half(Q.i0);
+    R[1] = Q.i1 + upper_half(Q.i1);
+    R[2] = Q.i2 + upper_half(Q.i2);
+}
+
 // ---- FP8 (OCP e4m3fn) pieces of the MX-MFMA inference kernels (width 128: nrc_kernels.hip; width 64: nrc_infer8.hip)
 typedef int i8v __attribute__((ext_vector_type(8)));  // 32 e4m3 bytes: one operand of the 32x32x64 MX MFMA
 

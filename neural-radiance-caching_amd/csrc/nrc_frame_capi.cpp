@@ -230,6 +230,11 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
                       (mode == NRC_RENDER_FULL || mode == NRC_RENDER_CACHE_ONLY);
     // knob "frame_sparse": zero-throughput pixels skip the MLP (nrc_infer_accumulate_sparse) on handles it supports
     const bool sparse = fuse && knob(kKnobFrameSparse) == 1 && net_infer_sparse_ok(net);
+    // knob "frame_factored_fused": the factored accumulation runs in the inference epilogue
+    // (nrc_infer_accumulate_factored) on handles it supports; the render queries' radiance is then not written
+    const bool rf_fused = rf && !p->keep_render_results && knob(kKnobFrameFactoredFused) == 1 &&
+                          net_infer_factored_ok(net);
+    const bool rf_fuse = rf_fused && (mode == NRC_RENDER_FULL || mode == NRC_RENDER_CACHE_ONLY);
     if ((uint64_t)screen + tiles > 0) require(qi && ri, "inference buffers are NULL");
     auto infer_range = [&](uint32_t first, uint32_t count, uint32_t acc_pixels) {
         // queries [first, first + count); the first acc_pixels of them are render queries of pixels first..
@@ -240,6 +245,10 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
             check(nrc_infer_accumulate_sparse(net, q, r, count, fb->last_render_throughput_d + first,
                                               fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode,
                                               p->iteration_index));
+        else if (rf_fuse && acc_pixels > 0)
+            check(nrc_infer_accumulate_factored(net, q, r, count, fb->last_render_throughput_d + first,
+                                                fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode,
+                                                p->iteration_index));
         else if (fuse && acc_pixels > 0)
             check(nrc_infer_accumulate(net, q, r, count, fb->last_render_throughput_d + first,
                                        fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode, p->iteration_index));
@@ -253,7 +262,7 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
         infer_range(screen, tiles, 0);
     }
     // Device::nrcAccumulateRadiance (Device.cpp:1310-1337)
-    if (!skip_render && !fuse && npix > 0) {
+    if (!skip_render && !fuse && !rf_fuse && npix > 0) {
         if (rf)
             check(accumulate_factored(fb->results_inference_d + p0, qi + (size_t)p0 * QD, fb->last_render_throughput_d + p0,
                                       fb->output_rgba_d + (size_t)p0 * 4, npix, mode, p->iteration_index, s, padq));
@@ -264,15 +273,19 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
     // Device::nrcVisualizeFirstRadiance (Device.cpp:1339-1370)
     if (mode == NRC_RENDER_CACHE_FIRST_VERTEX && npix > 0) {
         require(fb->queries_cache_vis_d && fb->results_cache_vis_d, "cache-vis buffers are NULL");
-        check(nrc_infer_stream(net, fb->queries_cache_vis_d + (size_t)p0 * QD,
-                               reinterpret_cast<float*>(fb->results_cache_vis_d + p0), npix, s));
-        if (rf)
-            check(accumulate_factored(fb->results_cache_vis_d + p0, fb->queries_cache_vis_d + (size_t)p0 * QD, nullptr,
-                                      fb->output_rgba_d + (size_t)p0 * 4, npix,
-                                      NRC_RENDER_DEBUG_CACHE_NO_THROUGHPUT_MODULATION, 0, s, padq));
-        else
-            check(nrc_copy_radiance_to_output(fb->results_cache_vis_d + p0, fb->output_rgba_d + (size_t)p0 * 4, npix,
-                                              s));
+        const float* qv = fb->queries_cache_vis_d + (size_t)p0 * QD;
+        float* rgba = fb->output_rgba_d + (size_t)p0 * 4;
+        if (rf_fused) {  // the factored copy_radiance_to_output_buffer in the epilogue; results_cache_vis stays unwritten
+            check(nrc_infer_accumulate_factored(net, qv, reinterpret_cast<float*>(fb->results_cache_vis_d + p0), npix,
+                                                nullptr, rgba, npix, NRC_RENDER_DEBUG_CACHE_NO_THROUGHPUT_MODULATION, 0));
+        } else {
+            check(nrc_infer_stream(net, qv, reinterpret_cast<float*>(fb->results_cache_vis_d + p0), npix, s));
+            if (rf)
+                check(accumulate_factored(fb->results_cache_vis_d + p0, qv, nullptr, rgba, npix,
+                                          NRC_RENDER_DEBUG_CACHE_NO_THROUGHPUT_MODULATION, 0, s, padq));
+            else
+                check(nrc_copy_radiance_to_output(fb->results_cache_vis_d + p0, rgba, npix, s));
+        }
     }
 
     // Training (Device.cpp:2505-2512): only when the trace produced records

@@ -38,6 +38,7 @@ constexpr int kL0H8 = 10 * 64;               // h8 (16-byte) units of the layer-
 constexpr int kImg8H8 = kInfer8ImgBytes / 16;  // ... of the FP8 fragments
 
 // fused accumulate_render_radiance (nrc_helpers.cu:77-129) for queries [0, n_acc): as InferEpilogue of nrc_kernels.hip
+// (factored modes: thr is not read in mode 4 and may be null)
 struct Accum8 {
     const float* thr;
     float4* rgba;
@@ -111,6 +112,10 @@ __device__ __forceinline__ void mlp8(lds_h8* lw_lane, const h8 (&x)[TILES][5], c
 }
 
 // EPI -1 plain, 0 / 2 fused accumulate_render_radiance (RenderMode Full / CacheOnly) for queries [0, n_acc).
+// EPI kInfer8Factored + 0 / 2 / 4: the same with USE_REFLECTANCE_FACTORING 1 (accumulate_kernel<MODE, true> of nrc_frame.hip,
+// operation for operation; 4 = DebugCacheNoThroughputModulation, the factored copy_radiance_to_output_buffer). The
+// reflectance diffuse + specular comes from the tile's QLane registers (reflectance_half0) before the prefetch
+// overwrites them: no memory traffic, three registers per tile live across the MLP.
 // wf: the handle's f16 inference image (its first 10 fragments are layer 0); img8: FP8 fragments + scale words.
 template <int EPI, int TILES, int THREADS>
 __global__ __launch_bounds__(THREADS, 1) void infer8_kernel(const float* __restrict__ q, float* __restrict__ out,
@@ -118,6 +123,8 @@ __global__ __launch_bounds__(THREADS, 1) void infer8_kernel(const float* __restr
                                                              const h8* __restrict__ img8, Accum8 epi) {
     __shared__ __attribute__((aligned(16))) h8 lw[kL0H8 + kImg8H8];
     __shared__ uint32_t wq_next;
+    constexpr bool RF = EPI >= kInfer8Factored;
+    constexpr int MODE = RF ? EPI - kInfer8Factored : EPI;  // the RenderMode of the epilogue (-1: none)
     fp32_flush_output_denorms();  // as the f16 kernel (same layer-0 / encoder arithmetic)
     fp8_saturating_converts();    // pack8
     for (int i = threadIdx.x; i < kL0H8; i += THREADS) lw[i] = wf[i];
@@ -161,6 +168,11 @@ __global__ __launch_bounds__(THREADS, 1) void infer8_kernel(const float* __restr
         h8 x[TILES][5];
 #pragma unroll
         for (int t = 0; t < TILES; ++t) encode_v3(Q[t], h, x[t]);
+        [[maybe_unused]] float R[TILES][3];
+        if constexpr (RF) {
+#pragma unroll
+            for (int t = 0; t < TILES; ++t) reflectance_half0(Q[t], R[t]);
+        }
         if (lane == 0) nn_raw = atomicAdd(&wq_next, 1u);  // the group after next
 #pragma unroll
         for (int t = 0; t < TILES; ++t)
@@ -173,14 +185,16 @@ __global__ __launch_bounds__(THREADS, 1) void infer8_kernel(const float* __restr
             for (int t = 0; t < TILES; ++t) {
                 const int64_t s0 = (g * TILES + t) * 32;
                 const int rows = tile_rows(epi.n_acc, s0);
-                const u3 tv = __builtin_amdgcn_raw_buffer_load_b96(buffer_rsrc(epi.thr + s0 * 3, rows * 12),
-                                                                   h ? kBufferOff : r * 12, 0, 0);
-                typedef float f3 __attribute__((ext_vector_type(3)));
-                const f3 tf = __builtin_bit_cast(f3, tv);  // whole-vector bit_cast (clang 22 element bit_cast bug)
-                tr[t][0] = tf.x;
-                tr[t][1] = tf.y;
-                tr[t][2] = tf.z;
-                if constexpr (EPI == 0) {
+                if constexpr (MODE != 4) {
+                    const u3 tv = __builtin_amdgcn_raw_buffer_load_b96(buffer_rsrc(epi.thr + s0 * 3, rows * 12),
+                                                                       h ? kBufferOff : r * 12, 0, 0);
+                    typedef float f3 __attribute__((ext_vector_type(3)));
+                    const f3 tf = __builtin_bit_cast(f3, tv);  // whole-vector bit_cast (clang 22 element bit_cast bug)
+                    tr[t][0] = tf.x;
+                    tr[t][1] = tf.y;
+                    tr[t][2] = tf.z;
+                }
+                if constexpr (MODE == 0) {
                     const u4 av = __builtin_amdgcn_raw_buffer_load_b128(buffer_rsrc(epi.rgba + s0, rows * 16),
                                                                         h ? kBufferOff : r * 16, 0, 0);
                     acc[t] = __builtin_bit_cast(float4, av);
@@ -199,7 +213,20 @@ __global__ __launch_bounds__(THREADS, 1) void infer8_kernel(const float* __restr
             bool to_out = h == 0;
             if constexpr (EPI >= 0) {
                 float4 v;
-                if constexpr (EPI == 0) {  // Full: dst += (T * L) * w
+                if constexpr (RF && MODE == 0) {  // Full: dst += ((T * L) * R) * w
+                    v = acc[t];
+                    v.x = __builtin_fmaf((tr[t][0] * L0) * R[t][0], epi.w, v.x);
+                    v.y = __builtin_fmaf((tr[t][1] * L1) * R[t][1], epi.w, v.y);
+                    v.z = __builtin_fmaf((tr[t][2] * L2) * R[t][2], epi.w, v.z);
+                } else if constexpr (RF && MODE == 2) {  // CacheOnly: (L * T) * R
+                    v.x = (L0 * tr[t][0]) * R[t][0];
+                    v.y = (L1 * tr[t][1]) * R[t][1];
+                    v.z = (L2 * tr[t][2]) * R[t][2];
+                } else if constexpr (RF) {  // copy_radiance_to_output_buffer: L * R
+                    v.x = L0 * R[t][0];
+                    v.y = L1 * R[t][1];
+                    v.z = L2 * R[t][2];
+                } else if constexpr (EPI == 0) {  // Full: dst += (T * L) * w
                     v = acc[t];
                     v.x = __builtin_fmaf(tr[t][0] * L0, epi.w, v.x);
                     v.y = __builtin_fmaf(tr[t][1] * L1, epi.w, v.y);
@@ -299,6 +326,9 @@ hipError_t launch8_modes(const float* queries, float* out, int64_t n, const _Flo
         case -1: return launch8<-1, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
         case 0: return launch8<0, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
         case 2: return launch8<2, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
+        case kInfer8Factored + 0: return launch8<kInfer8Factored + 0, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
+        case kInfer8Factored + 2: return launch8<kInfer8Factored + 2, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
+        case kInfer8Factored + 4: return launch8<kInfer8Factored + 4, TILES, THREADS>(queries, out, n, wf, img8, epi, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -248,8 +248,10 @@ __host__ __device__ constexpr int f8_row64(int h, int j) {
 }
 // the FP8 image + scales from the f32 inference weights (no host synchronisation: legal in a captured graph)
 hipError_t launch_pack8(const float* w_infer, uint8_t* img8, hipStream_t s);
-// wf: the f16 inference image (layer 0); mode -1 plain, 0 / 2 fused accumulation for queries [0, n_acc);
+// wf: the f16 inference image (layer 0); mode -1 plain, 0 / 2 fused accumulation for queries [0, n_acc),
+// kInfer8Factored + 0 / 2 / 4 its reflectance-factored form (4 = DebugCacheNoThroughputModulation; thr is not read);
 // variant 0 = the product shape, 1 = the A/B loser (debug library, plain output only; else hipErrorNotSupported)
+constexpr int kInfer8Factored = 10;
 hipError_t launch_infer8(int variant, const float* queries, float* out, int64_t n, const _Float16* wf,
                          const uint8_t* img8, const float* thr, float* rgba, int64_t n_acc, int mode, float w,
                          hipStream_t s);
@@ -282,6 +284,11 @@ constexpr int kSparseChunk = 2048;
 hipError_t launch_infer_accumulate_sparse(const float* queries, float* out, int64_t n, const _Float16* wf,
                                           const float* thr, float* rgba, int64_t n_acc, int mode, float w,
                                           hipStream_t s);
+// inference with the reflectance-factored accumulate_render_radiance fused for queries [0, n_acc) (nrc_infer_factored.hip):
+// width 64, Frequency, F16, compact queries; mode 0 Full / 2 CacheOnly / 4 DebugCacheNoThroughputModulation (thr not read)
+hipError_t launch_infer_accumulate_factored(const float* queries, float* out, int64_t n, const _Float16* wf,
+                                            const float* thr, float* rgba, int64_t n_acc, int mode, float w,
+                                            hipStream_t s);
 // InputEncoding::Hash inference (mode -1: plain; 0 / 2: fused accumulation for queries [0, n_acc))
 // feat: the handle's [NRC_HASH_LEVELS][kHashFeatStride] level-feature workspace (hash_feature_kernel, round 3), or
 // nullptr for the round-2 gather kernel (also knob "hash_infer" = 1)
@@ -433,7 +440,10 @@ enum Knob : int {
                               // at s_setprio 1 (-1 / 0: no priority)
     kKnobFrameSparse = 19,    // nrc_process_frame / _shard: 1 = the fused Full / CacheOnly inference through
                               // nrc_infer_accumulate_sparse on handles it supports (-1 / 0: the dense kernel)
-    kKnobCount = 20
+    kKnobFrameFactoredFused = 20,  // nrc_process_frame / _shard with reflectance_factoring: 1 = the factored accumulation
+                                   // in the inference epilogue (nrc_infer_accumulate_factored) on handles it supports
+                                   // (-1 / 0: infer + the factored accumulation kernel)
+    kKnobCount = 21
 };
 int knob(Knob k);
 
@@ -567,6 +577,8 @@ bool net_padq(nrc_net* net);
 bool net_infer_fusable(nrc_net* net);
 // nrc_infer_accumulate_sparse serves the handle (width 64, Frequency, F16, compact queries)
 bool net_infer_sparse_ok(nrc_net* net);
+// nrc_infer_accumulate_factored serves the handle (width 64, Frequency, F16 or FP8, compact queries)
+bool net_infer_factored_ok(nrc_net* net);
 // throws NRC_ERR_INTERNAL if a training kernel or a peer-exchange wait reported a timeout (after a stream sync)
 void net_check_protocol(nrc_net* net);
 // nrc_train_dp with the loss left in a device slot (frame driver)

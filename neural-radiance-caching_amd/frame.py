@@ -84,6 +84,7 @@ def _sigs():
         "nrc_copy_radiance_to_output": [vp, vp, u32, vp],
         "nrc_infer_accumulate": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
         "nrc_infer_accumulate_sparse": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
+        "nrc_infer_accumulate_factored": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
         "nrc_propagate_train_radiance": [vp, vp, u32, vp, vp, u32, vp],
         "nrc_accumulate_render_radiance_factored": [vp, vp, vp, vp, u32, ctypes.c_int, u32, vp],
         "nrc_copy_radiance_to_output_factored": [vp, vp, vp, u32, vp],
@@ -170,6 +171,18 @@ def infer_accumulate_sparse(net, queries, results, n: int, throughput, output_rg
     check(_sigs().nrc_infer_accumulate_sparse(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
                                               _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
                                               int(num_pixels), int(mode), int(iteration_index)))
+
+
+def infer_accumulate_factored(net, queries, results, n: int, throughput, output_rgba, num_pixels: int,
+                              mode: RenderMode, iteration_index: int) -> None:
+    """infer_accumulate() for USE_REFLECTANCE_FACTORING 1: the render queries' radiance times their reflectance
+    (diffuse + specular, from the query registers) goes into ``output_rgba`` bit for bit as infer() followed by
+    accumulate_render_radiance_factored() puts it (frame.h). Modes Full, CacheOnly and
+    DebugCacheNoThroughputModulation (``throughput`` may be None). Width 64, Frequency, F16 or FP8, compact queries;
+    other handles raise NrcError (NRC_ERR_UNSUPPORTED)."""
+    check(_sigs().nrc_infer_accumulate_factored(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
+                                                _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
+                                                int(num_pixels), int(mode), int(iteration_index)))
 
 
 def copy_radiance_to_output(radiance, output_rgba, num_pixels: int, stream=None) -> None:
