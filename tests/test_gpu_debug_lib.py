@@ -69,7 +69,16 @@ def test_debug_library_variants_in_subprocess():
            "tests/test_gpu_fp8_64.py::test_two_tile_variant_bitwise",
            "tests/test_gpu_debug_lib.py::test_debug_entry_points",
            "tests/test_gpu_train_dc.py::test_dc_gradient_is_deterministic_with_a_slow_dw_wave",
-           "tests/test_gpu_train_dc.py::test_dc_protocol_timeout_is_reported"]
+           "tests/test_gpu_train_dc.py::test_dc_protocol_timeout_is_reported",
+           # the debug build's production kernels over the whole query domain (tests/test_gpu_domain.py)
+           "tests/test_gpu_domain.py::test_encoders_on_the_domain",
+           "tests/test_gpu_domain.py::test_inference_on_the_domain[f16]",
+           "tests/test_gpu_domain.py::test_inference_on_the_domain[fp8_64]",
+           "tests/test_gpu_domain.py::test_inference_on_the_domain[hash]",
+           "tests/test_gpu_domain.py::test_gradient_blocks_on_the_domain[frequency-1000]",
+           "tests/test_gpu_domain.py::test_gradient_blocks_on_the_domain[frequency-4608]",
+           "tests/test_gpu_domain.py::test_gradient_blocks_on_the_domain[hash-1000]",
+           "tests/test_gpu_domain.py::test_training_ignores_rows_past_b"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     print(r.stdout[-3000:])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
