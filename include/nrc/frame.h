@@ -10,6 +10,7 @@
  *   propagate_train_radiance                       nrc_helpers.cu:131-224 -> nrc_propagate_train_radiance
  *   generateRandomPermutationForTrain              NRCUtil.cu:19-35       -> nrc_generate_train_permutation
  *   permute_train_data                             nrc_helpers.cu:226-249 -> nrc_permute_train_data
+ *   permute_train_data + Network::train (fused)                           -> nrc_train_gather
  *   NUM_BATCHES x train                            Device.cpp:1473-1512   -> nrc_train
  *
  * Same conventions as nrc_c.h: plain device pointers, int status, stream-ordered, never throws.
@@ -180,6 +181,27 @@ nrc_status nrc_permute_train_data(const float* queries_src_d, const nrc_float3* 
                                   int32_t num_records, float* queries_dst_d, nrc_float3* targets_dst_d,
                                   uint32_t n_out, hipStream_t stream);
 
+/* One optimizer step on samples gathered straight from the traced buffers. Sample d in [0, b) is
+ *     s = perm(first + d) % min(num_records, n_out);  query = queries_src[s];  target = targets_src[s]
+ * with perm exactly as nrc_permute_train_data defines it: permutation_d[first + d] if permutation_d != NULL, else the
+ * Feistel permutation of (seed, frame_index) on [0, n_out).
+ * Result: bit for bit the parameters, Adam moments, EMA, inference weights and loss of
+ *     nrc_permute_train_data(..., n_out) followed by nrc_train_async on rows [first, first + b) of its output
+ * -- the shuffled copy is never written: the training kernel's sample loads read the source records themselves
+ * (DESIGN.md §9 "Gathered training step"). On the handle's stream; never blocks; loss_d (device, may be NULL) as
+ * nrc_train_async. The record size follows the handle's nrc_config.query_layout (compact 15 or padded 16 floats).
+ * Arguments: num_records >= 1 (unlike nrc_permute_train_data, where <= 0 is a no-op: there is nothing to train on),
+ * 1 <= n_out <= 2^30, b >= 1, first + b <= n_out; anything else is NRC_ERR_INVALID_ARGUMENT. Only entries
+ * [first, first + b) of permutation_d are read; an entry is reduced as an unsigned value, so no entry can address a
+ * record outside [0, min(num_records, n_out)).
+ * Handles: width 64, NRC_ENCODING_FREQUENCY, compact or padded queries, any infer_precision (an FP8 handle's inference
+ * image is repacked after the step as after nrc_train_async), the production training kernels (knobs train_kernel,
+ * train_shape, t16_groups at default). Hash, FrequencySH and width 128 are NRC_ERR_UNSUPPORTED with a message that
+ * names the combination. */
+nrc_status nrc_train_gather(nrc_net* net, const float* queries_src_d, const nrc_float3* targets_src_d,
+                            const int32_t* permutation_d, uint64_t seed, uint32_t frame_index, int32_t num_records,
+                            uint32_t n_out, uint32_t first, uint32_t b, float* loss_d);
+
 /* The entry points above that read RadianceQuery records, for padded 16-float records (USE_COMPACT_RADIANCE_QUERY 0,
  * layout.h; the reference's same kernels compiled with the other struct). nrc_process_frame follows the handle's
  * nrc_config.query_layout by itself. */
@@ -212,8 +234,10 @@ typedef struct nrc_frame_buffers {
     nrc_float3* results_cache_vis_d;              /* [screen], CacheFirstVertex only */
     const nrc_train_suffix_end_vertex* end_vertices_d; /* [tiles] */
     const nrc_training_record* train_records_d;   /* [65536] */
-    float* train_queries_d[2];                    /* DoubleBuffer<RadianceQuery>: [0] as traced, [1] shuffled */
-    nrc_float3* train_targets_d[2];               /* DoubleBuffer<float3>: [0] emission so far (+= propagation) */
+    float* train_queries_d[2];                    /* DoubleBuffer<RadianceQuery>: [0] as traced, [1] shuffled (not
+                                                     written when the steps gather, knob "frame_train_gather") */
+    nrc_float3* train_targets_d[2];               /* DoubleBuffer<float3>: [0] emission so far (+= propagation);
+                                                     [1] shuffled (not written when the steps gather) */
     const int32_t* permutation_d;                 /* NULL: the key sort below, or the Feistel permutation of
                                                      (shuffle_seed, frame_index) */
     const uint32_t* shuffle_keys_d;               /* [65536] keys whose stable sort gives the permutation
@@ -245,6 +269,12 @@ typedef struct nrc_frame_params {
  * "frame_factored_fused" = 1 (nrc_c.h), the epilogue of nrc_infer_accumulate_factored: Full / CacheOnly over the render +
  * tile launch (whole frame and shard range alike), CacheFirstVertex in mode 4 over the cache-vis queries. Factored
  * propagation and everything after it are the same either way, and so is the frame buffer, bit for bit.
+ * Under the process-wide knob "frame_train_gather" = 1 (nrc_c.h), on a handle nrc_train_gather serves and with no
+ * communicator or peer exchange attached, the shuffle launches no copy: the NUM_BATCHES steps are nrc_train_gather on
+ * train_queries_d[0] / train_targets_d[0] with first = batch * 16384 and the same permutation (the caller's, else the
+ * sorted keys, else Feistel). Network state and losses are bit for bit those of the copying sequence;
+ * train_queries_d[1] and train_targets_d[1] are then NOT written (they must still be non-NULL). Data-parallel frames
+ * and every other handle take the copying sequence whatever the knob says.
  * loss_h (optional) receives the mean of the NUM_BATCHES minibatch losses (Device.cpp:1503-1511) and makes the call
  * block once at the end (the reference blocks after every minibatch); 0 if the frame did not train. */
 nrc_status nrc_process_frame(nrc_net* net, const nrc_frame_buffers* buffers, const nrc_frame_params* params,

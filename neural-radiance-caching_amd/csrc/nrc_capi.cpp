@@ -264,13 +264,13 @@ bool want_t16(int encoding) {
     return encoding == NRC_ENCODING_FREQUENCY || encoding == NRC_ENCODING_HASH;
 }
 
-std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 const char* const kKnobNames[kKnobCount] = {"train_kernel", "train_shape", "scatter_min", "scatter_max", "dc_dw0_delay",
                                             "hash_infer", "hash_feat_abl", "t16_groups", "hash_feat_p", "peer_path",
                                             "px_polls", "scatter_part", "scatter_compact", "hash_train_feat",
                                             "hash_adam", "train_fused", "fuse_mode", "tcnn_reentry", "train_prio",
-                                            "frame_sparse", "frame_factored_fused"};
-static_assert(kKnobCount == 21, "one initial value and one name per knob");
+                                            "frame_sparse", "frame_factored_fused", "frame_train_gather"};
+static_assert(kKnobCount == 22, "one initial value and one name per knob");
 
 std::string config_json(int encoding, const nrc_config& c) {
     char buf[2048];
@@ -862,6 +862,42 @@ void do_train(nrc_net* net, const float* in, const float* tgt, uint32_t b, float
     }
 }
 
+// why nrc_train_gather cannot serve a b-sample step of the handle (names the combination), or null. The gather forms
+// exist for the two production Frequency kernels; a knob that selects another kernel or block shape is refused too.
+const char* train_gather_unsupported(const nrc_net* net, uint32_t b) {
+    if (net->wide()) return "gathered training step: width 128 is not supported (width 64 only)";
+    if (net->hash()) return "gathered training step: InputEncoding::Hash is not supported (Frequency only)";
+    if (net->encoding == NRC_ENCODING_FREQUENCY_SH)
+        return "gathered training step: InputEncoding::FrequencySH is not supported (Frequency only)";
+    const bool dc = net->t16 && net->t16_kernel == 0 && dc_shape(b) >= 0;
+    if (!net->t16 || net->t16_kernel == 2 || (dc ? dc_shape(b) != 7 : t16_groups() != 2))
+        return "gathered training step: the production training kernels only (knobs train_kernel, train_shape, "
+               "t16_groups at default)";
+    return nullptr;
+}
+
+// nrc_train_gather: do_train's two-launch Frequency step with the gather form of its training kernel. The reduce /
+// Adam launch sees the same per-block slabs and loss partials in the same order, so the step is bitwise do_train's on
+// the permuted rows (a handle that fuses the step into one launch, knob train_fused, is bitwise the two launches too).
+void do_train_gather(nrc_net* net, const float* qs, const float* ts, const GatherSrc& gs, uint32_t b, float* loss_d) {
+    const int blocks = train_block_count(net, b);
+    net->ensure_slabs(blocks);
+    net->check_protocol();
+    const float n_total = 3.0f * (float)b;
+    _Float16* const slabs = reinterpret_cast<_Float16*>(net->slabs);
+    if (net->t16_kernel == 0 && dc_shape(b) >= 0)
+        HIP_CHECK(launch_train_dc_gather(dc_shape(b), qs, ts, gs, b, n_total, net->cfg.loss_scale, net->wf_train,
+                                         net->wb_train, slabs, net->loss_partials, net->proto_err_dev(), net->stream,
+                                         net->padq()));
+    else
+        HIP_CHECK(launch_train16_gather(qs, ts, gs, b, n_total, net->cfg.loss_scale, net->wf_train, net->wb_train, slabs,
+                                        net->loss_partials, net->stream, net->padq()));
+    net->step += 1;
+    HIP_CHECK(launch_reduce_adam(kReduceFused, net->slabs, blocks, net->loss_partials, nullptr,
+                                 loss_d ? loss_d : net->loss_dev, net->buffers(), net->optim(net->step), net->stream));
+    pack_fp8_64(net, net->stream);
+}
+
 int wide_enc(const nrc_net* net) { return net->encoding == NRC_ENCODING_FREQUENCY_SH ? 2 : 0; }
 
 hipError_t infer_wide(nrc_net* net, int prec, const float* in, float* out, uint32_t n, const float* thr, float* rgba,
@@ -1018,6 +1054,11 @@ bool nrc_amd::net_infer_factored_ok(nrc_net* net) {
     return factored_unsupported(net) == nullptr;
 }
 
+bool nrc_amd::net_train_gather_ok(nrc_net* net, uint32_t b) {
+    check_live(net);
+    return train_gather_unsupported(net, b) == nullptr;
+}
+
 void nrc_amd::net_check_protocol(nrc_net* net) {
     check_live(net);
     net->check_protocol();
@@ -1060,6 +1101,7 @@ bool knob_value_ok(Knob k, int v) {
         case kKnobTrainPrio: return v >= -1 && v <= 2;
         case kKnobFrameSparse: return v >= -1 && v <= 1;
         case kKnobFrameFactoredFused: return v >= -1 && v <= 1;
+        case kKnobFrameTrainGather: return v >= -1 && v <= 1;
         default: return false;
     }
 }
@@ -1334,6 +1376,25 @@ nrc_status nrc_train_async(nrc_net* net, const float* in, const float* tgt, uint
         check_live(net);
         // loss_d == NULL: the loss still lands in the handle's own slot
         do_train(net, in, tgt, b, nullptr, loss_d);
+    });
+}
+
+nrc_status nrc_train_gather(nrc_net* net, const float* qs, const nrc_float3* ts, const int32_t* perm, uint64_t seed,
+                            uint32_t frame_index, int32_t num_records, uint32_t n_out, uint32_t first, uint32_t b,
+                            float* loss_d) {
+    return guarded([&] {
+        check_live(net);
+        if (num_records <= 0) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "num_records must be >= 1");
+        if (n_out == 0 || n_out > (1u << 30)) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "n_out must be in 1..2^30");
+        if (b == 0) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "batch size must be >= 1");
+        if ((uint64_t)first + b > n_out) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "first + b must be <= n_out");
+        if (const char* why = train_gather_unsupported(net, b)) throw ApiError(NRC_ERR_UNSUPPORTED, why);
+        if (!qs || !ts) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "null query/target pointer");
+        if ((reinterpret_cast<uintptr_t>(qs) | reinterpret_cast<uintptr_t>(ts) | reinterpret_cast<uintptr_t>(perm)) & 3)
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "buffers must be 4-byte aligned");
+        const GatherSrc gs{perm, make_key(seed, frame_index, n_out), first,
+                           (uint32_t)std::min<int64_t>(num_records, (int64_t)n_out)};  // nrc_helpers.cu:236
+        do_train_gather(net, qs, reinterpret_cast<const float*>(ts), gs, b, loss_d);
     });
 }
 

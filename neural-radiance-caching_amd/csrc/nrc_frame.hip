@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "nrc_internal.h"
+#include "nrc_shuffle.h"
 
 namespace nrc_amd {
 
@@ -141,38 +142,7 @@ __global__ __launch_bounds__(256) void propagate_kernel(const EndVertex* __restr
     }
 }
 
-// ---- shuffle permutation: keyed 4-round Feistel network on [0, 2^(2h)) with cycle walking into [0, n).
-// Spec in DESIGN.md §9 (restated independently in oracle/nrc_frame_oracle.c).
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-struct FeistelKey {
-    uint32_t k[4];
-    uint32_t h, n;
-};
-
-__device__ __forceinline__ uint32_t feistel_perm(uint32_t d, const FeistelKey& fk) {
-    const uint32_t mask = (1u << fk.h) - 1u;
-    uint32_t x = d;
-    do {
-        uint32_t L = x >> fk.h, R = x & mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t nl = R;
-            R = L ^ (mix32(R ^ fk.k[r]) & mask);
-            L = nl;
-        }
-        x = (L << fk.h) | R;
-    } while (x >= fk.n);  // terminates: the walk stays on d's cycle, which contains d < n
-    return x;
-}
-
+// ---- shuffle permutation: the keyed Feistel network of nrc_shuffle.h (mix32, FeistelKey, feistel_perm, make_key)
 __global__ __launch_bounds__(256) void permutation_kernel(FeistelKey fk, int* __restrict__ perm) {
     const uint32_t d = blockIdx.x * 256u + threadIdx.x;
     if (d >= fk.n) return;
@@ -339,26 +309,6 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const uint32_t* __res
             scatter_group(g0);
         }
     }
-}
-
-FeistelKey make_key(uint64_t seed, uint32_t frame, uint32_t n) {
-    auto mix = [](uint32_t x) {
-        x ^= x >> 16;
-        x *= 0x7feb352du;
-        x ^= x >> 15;
-        x *= 0x846ca68bu;
-        x ^= x >> 16;
-        return x;
-    };
-    FeistelKey fk{};
-    for (uint32_t r = 0; r < 4; ++r)
-        fk.k[r] = mix((uint32_t)seed ^ mix((uint32_t)(seed >> 32) ^ mix(frame + 0x9e3779b9u * (r + 1))));
-    uint32_t b = 2;
-    while (b < 32 && (1ull << b) < (uint64_t)n) ++b;
-    if (b & 1) ++b;
-    fk.h = b / 2;
-    fk.n = n;
-    return fk;
 }
 
 inline dim3 grid_for(uint64_t threads) { return dim3((unsigned)((threads + 255) / 256)); }

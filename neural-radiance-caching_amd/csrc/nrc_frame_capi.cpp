@@ -311,15 +311,19 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
         HIP_CHECK(launch_sort_pairs(fb->shuffle_keys_d, nullptr, sorted, N, scratch + sizeof(int32_t) * N, s));
         perm = sorted;
     }
-    check(permute_train(fb->train_queries_d[0], fb->train_targets_d[0], perm, p->shuffle_seed,
-                        p->frame_index, nrec, fb->train_queries_d[1], fb->train_targets_d[1],
-                        NRC_NUM_TRAINING_RECORDS_PER_FRAME, s, padq));
+    int rank = 0, world = 1;
+    const bool dp = net_comm(net, &rank, &world);
+    // knob "frame_train_gather": no shuffled copy, every step reads its samples from the traced buffers through the
+    // permutation (nrc_train_gather); the [1] buffers stay unwritten. Not for data-parallel slices.
+    const bool gather = !dp && knob(kKnobFrameTrainGather) == 1 && net_train_gather_ok(net, NRC_BATCH_SIZE);
+    if (!gather)
+        check(permute_train(fb->train_queries_d[0], fb->train_targets_d[0], perm, p->shuffle_seed,
+                            p->frame_index, nrec, fb->train_queries_d[1], fb->train_targets_d[1],
+                            NRC_NUM_TRAINING_RECORDS_PER_FRAME, s, padq));
     // Device::nrcTrainRadiance (Device.cpp:1473-1512): NUM_BATCHES steps, mean loss. The minibatch losses
     // land in host-mapped slots and are read after one sync at the end (the reference syncs after
     // every minibatch, Device.cpp:1504); summed in the same order, so the mean is the same float.
     const nrc_loss_slots slots = net_loss_slots(net);
-    int rank = 0, world = 1;
-    const bool dp = net_comm(net, &rank, &world);
     // this rank's slice of every minibatch (dp::shard_range): sizes differ by at most one sample
     const uint32_t base = NRC_BATCH_SIZE / world, rem = NRC_BATCH_SIZE % world;
     const uint32_t s0 = rank * base + std::min<uint32_t>(rank, rem), sn = base + (rank < (int)rem ? 1 : 0);
@@ -327,7 +331,11 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
         const size_t first = (size_t)b * NRC_BATCH_SIZE + (dp ? s0 : 0);
         const float* bq = fb->train_queries_d[1] + first * QD;
         const float* bt = reinterpret_cast<const float*>(fb->train_targets_d[1] + first);
-        if (dp)
+        if (gather)
+            check(nrc_train_gather(net, fb->train_queries_d[0], fb->train_targets_d[0], perm, p->shuffle_seed,
+                                   p->frame_index, nrec, NRC_NUM_TRAINING_RECORDS_PER_FRAME,
+                                   (uint32_t)b * NRC_BATCH_SIZE, NRC_BATCH_SIZE, slots.dev + b));
+        else if (dp)
             net_train_dp_async(net, bq, bt, sn, NRC_BATCH_SIZE, slots.dev + b);
         else
             check(nrc_train_async(net, bq, bt, NRC_BATCH_SIZE, slots.dev + b));

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "nrc/layout.h"
+#include "nrc_shuffle.h"
 
 // 1 in libnrc_amd_debug.so: diagnostic builds (phase stamps, in-kernel clocks) and the A/B kernels that lost their
 // comparisons; 0 in the product library libnrc_amd.so
@@ -370,6 +371,11 @@ struct ModelBuffers {
 hipError_t launch_train16(const float* queries, const float* targets, int64_t b, float n_total, float loss_scale,
                           const _Float16* wf, const _Float16* wb, _Float16* slabs, float* loss_partials, uint64_t* stamps,
                           hipStream_t s, bool split = false, int groups = 2, bool padq = false);
+// nrc_train_gather on the role-split kernel (128-sample blocks): launch_train16's slabs and loss partials with sample d
+// read from record perm(gs.first + d) % gs.nrec of the traced buffers (nrc_shuffle.h)
+hipError_t launch_train16_gather(const float* queries_src, const float* targets_src, const GatherSrc& gs, int64_t b,
+                                 float n_total, float loss_scale, const _Float16* wf, const _Float16* wb,
+                                 _Float16* slabs, float* loss_partials, hipStream_t s, bool padq);
 // Round 6: one launch for the whole width-64 Frequency step of the role-split kernel (128-sample blocks): trainer
 // blocks + reducer blocks that wait for them on the counters at sync (2 x 256 B, zero at allocation) and then run
 // kReduceFused's sums and Adam/EMA from agent-scope loads of the slabs -- state bitwise the same as
@@ -405,6 +411,10 @@ hipError_t launch_train_dc(int shape, const float* queries, const float* targets
                            float loss_scale, const _Float16* wf, const _Float16* wb, _Float16* slabs,
                            float* loss_partials, uint32_t* err, hipStream_t s, uint64_t* stamps = nullptr, bool padq = false);
 int dc_waves_per_block(int shape);
+// nrc_train_gather on the decoupled-chain kernel: the production shape (dc_auto_shape, 7) only
+hipError_t launch_train_dc_gather(int shape, const float* queries_src, const float* targets_src, const GatherSrc& gs,
+                                  int64_t b, float n_total, float loss_scale, const _Float16* wf, const _Float16* wb,
+                                  _Float16* slabs, float* loss_partials, uint32_t* err, hipStream_t s, bool padq);
 // the production shape for a batch of b samples
 int dc_auto_shape(int64_t b);
 
@@ -443,7 +453,10 @@ enum Knob : int {
     kKnobFrameFactoredFused = 20,  // nrc_process_frame / _shard with reflectance_factoring: 1 = the factored accumulation
                                    // in the inference epilogue (nrc_infer_accumulate_factored) on handles it supports
                                    // (-1 / 0: infer + the factored accumulation kernel)
-    kKnobCount = 21
+    kKnobFrameTrainGather = 21,    // nrc_process_frame / _shard: 1 = no permute_train_data launch, the NUM_BATCHES steps
+                                   // gather from the traced buffers (nrc_train_gather) on handles it serves, outside
+                                   // data-parallel mode (-1 / 0: permute, then train on the shuffled buffers)
+    kKnobCount = 22
 };
 int knob(Knob k);
 
@@ -579,6 +592,8 @@ bool net_infer_fusable(nrc_net* net);
 bool net_infer_sparse_ok(nrc_net* net);
 // nrc_infer_accumulate_factored serves the handle (width 64, Frequency, F16 or FP8, compact queries)
 bool net_infer_factored_ok(nrc_net* net);
+// nrc_train_gather serves a b-sample step of the handle (width 64, Frequency, the production training kernels)
+bool net_train_gather_ok(nrc_net* net, uint32_t b);
 // throws NRC_ERR_INTERNAL if a training kernel or a peer-exchange wait reported a timeout (after a stream sync)
 void net_check_protocol(nrc_net* net);
 // nrc_train_dp with the loss left in a device slot (frame driver)

@@ -93,11 +93,17 @@ struct Stamper {
     }
 };
 
-template <int CW, int GPW, int DWW, bool STAMP, bool PADQ = false>  // PADQ: padded RadianceQuery records
+// GATHER 1 / 2 (nrc_train_gather; 1 a permutation array, 2 Feistel): q / t are the traced buffers and sample d is
+// their record perm(gs.first + d) % gs.nrec (nrc_shuffle.h). A chain wave holds one 16-sample group, so every lane
+// derives its own sample's row (the four lane groups in step: one instruction stream). The permutation entry is
+// the wave's first load and layer 0's twelve fragments go out behind it, so the index -> row hop overlaps loads the
+// dense kernel waits for at the same place (the encoder's operands and w0 are both needed by layer 0).
+template <int CW, int GPW, int DWW, bool STAMP, bool PADQ = false, int GATHER = 0>  // PADQ: padded RadianceQuery records
 __device__ __forceinline__ void dc_chain(const float* __restrict__ q, const float* __restrict__ t, int64_t b,
                                          float n_total, float loss_scale, const h8* __restrict__ wf,
                                          const h8* __restrict__ wb, char* smem, int cw, int lane, uint32_t* err,
-                                         const Stamper<STAMP>& stamp) {
+                                         const Stamper<STAMP>& stamp, const GatherSrc& gs = GatherSrc{}) {
+    static_assert(!GATHER || GPW == 1, "the gather form is the production shape: one group per chain wave");
     using Lay = DcLayout<CW, GPW>;
     constexpr int S = Lay::S;
     uint32_t* flags = (uint32_t*)(smem + Lay::OFF_FLAGS);
@@ -113,12 +119,25 @@ __device__ __forceinline__ void dc_chain(const float* __restrict__ q, const floa
     float pq[GPW][3], bl[GPW][2], iv[GPW][2], tg[GPW][3];
     [[maybe_unused]] float pad[GPW];
     constexpr int X = PADQ ? 1 : 0;
+    h8 w0[12], wA[8], wB[8], wC[8];
+    [[maybe_unused]] uint32_t p = 0;  // GATHER: perm(first + d) of this lane's sample
+    if constexpr (GATHER) {
+        // padding samples (past b) take the step's last sample, as the dense kernel reads it
+        const int64_t sl = (int64_t)blockIdx.x * S + 16 * cw + c;
+        const uint32_t i = gs.first + (uint32_t)(sl < b ? sl : b - 1);
+        if constexpr (GATHER == 1) p = (uint32_t)gs.perm[i];
+#pragma unroll
+        for (int f = 0; f < 12; ++f) w0[f] = wf[f * 64 + lane];  // layer 0 = fragments 0..11 (t16_fwd_frag)
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (GATHER == 2) p = feistel_perm(i, gs.fk);
+    }
 #pragma unroll
     for (int u = 0; u < GPW; ++u) {
         r[u] = 16 * GPW * cw + 16 * u + c;
         const int64_t s = (int64_t)blockIdx.x * S + r[u];
         valid[u] = s < b;
-        const int64_t sc = valid[u] ? s : b - 1;
+        int64_t sc = valid[u] ? s : b - 1;
+        if constexpr (GATHER) sc = p % gs.nrec;
         // position (+ pad_), OneBlob dims 3 + 2g, 4 + 2g, Identity dims 9 + 2g, 10 + 2g (lane group 3: dummies with
         // zero weights, fed from group 0's dims so that they stay finite), target
         const float* qr = q + sc * (NRC_INPUT_DIMS + X);
@@ -132,11 +151,12 @@ __device__ __forceinline__ void dc_chain(const float* __restrict__ q, const floa
 #pragma unroll
         for (int k = 0; k < 3; ++k) tg[u][k] = t[sc * 3 + k];
     }
-    h8 w0[12], wA[8], wB[8], wC[8];
+    if constexpr (!GATHER) {
 #pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
+        for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-        for (int ks = 0; ks < 3; ++ks) w0[mb * 3 + ks] = wf[t16_fwd_frag(0, mb, ks) * 64 + lane];
+            for (int ks = 0; ks < 3; ++ks) w0[mb * 3 + ks] = wf[t16_fwd_frag(0, mb, ks) * 64 + lane];
+    }
     load8(wf, t16_fwd_frag(1, 0, 0), lane, wA);
     load8(wf, t16_fwd_frag(2, 0, 0), lane, wB);
     __builtin_amdgcn_sched_barrier(0);
@@ -435,6 +455,27 @@ __global__ __launch_bounds__(64 * (CW + DWW), (CW + DWW + 3) / 4) void train_dc_
     stamp.real(15);
 }
 
+// The gather form of train_dc_kernel<CW, GPW, DWW, false, PADQ> (nrc_train_gather): same blocks, slabs and loss
+// partials. SRC: 1 permutation array, 2 Feistel.
+template <int CW, int GPW, int DWW, bool PADQ, int SRC>
+__global__ __launch_bounds__(64 * (CW + DWW), (CW + DWW + 3) / 4) void train_dc_gather_kernel(
+    const float* __restrict__ q, const float* __restrict__ t, int64_t b, float n_total, float loss_scale,
+    const h8* __restrict__ wf, const h8* __restrict__ wb, _Float16* __restrict__ slabs, float* __restrict__ loss_partials,
+    uint32_t* err, GatherSrc gs) {
+    using Lay = DcLayout<CW, GPW>;
+    __shared__ __attribute__((aligned(16))) char smem[Lay::BYTES];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const Stamper<false> stamp{nullptr, lane};
+    if (threadIdx.x < 16) ((uint32_t*)(smem + Lay::OFF_FLAGS))[threadIdx.x] = 0;
+    __syncthreads();
+    if (wave < CW)
+        dc_chain<CW, GPW, DWW, false, PADQ, SRC>(q, t, b, n_total, loss_scale, wf, wb, smem, wave, lane, err, stamp, gs);
+    else
+        dc_dw<CW, GPW, DWW, false>(smem, wave - CW, lane, slabs + (int64_t)blockIdx.x * slab_floats(0), loss_partials,
+                                   err, stamp);
+}
+
 template <int CW, int GPW, int DWW, bool PADQ = false>
 hipError_t launch_dc(const float* q, const float* t, int64_t b, float n_total, float loss_scale, const _Float16* wf,
                      const _Float16* wb, _Float16* slabs, float* loss_partials, uint32_t* err, hipStream_t s,
@@ -525,6 +566,27 @@ hipError_t launch_train_dc(int shape, const float* queries, const float* targets
         case 7: return launch_dc<2, 1, 4>(queries, targets, b, n_total, loss_scale, wf, wb, slabs, loss_partials, err, s, stamps);
         default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_train_dc_gather(int shape, const float* queries_src, const float* targets_src, const GatherSrc& gs,
+                                  int64_t b, float n_total, float loss_scale, const _Float16* wf, const _Float16* wb,
+                                  _Float16* slabs, float* loss_partials, uint32_t* err, hipStream_t s, bool padq) {
+    if (b <= 0) return hipSuccess;
+    if (!err) return hipErrorInvalidValue;
+    if (shape != 7) return hipErrorNotSupported;
+    // every row the kernel forms stays below nrec; every permutation index below first + b <= n_out
+    if (gs.nrec == 0 || gs.nrec > gs.fk.n || (uint64_t)gs.first + (uint64_t)b > gs.fk.n) return hipErrorInvalidValue;
+    constexpr int CW = 2, GPW = 1, DWW = 4, S = DcLayout<CW, GPW>::S;
+    const dim3 grid((unsigned)((b + S - 1) / S)), block(64 * (CW + DWW));
+#define NRC_DC_GATHER(PADQ, SRC)                                                                                       \
+    hipLaunchKernelGGL((train_dc_gather_kernel<CW, GPW, DWW, PADQ, SRC>), grid, block, 0, s, queries_src, targets_src, \
+                       b, n_total, loss_scale, (const h8*)wf, (const h8*)wb, slabs, loss_partials, err, gs)
+    if (padq && gs.perm) NRC_DC_GATHER(true, 1);
+    else if (padq) NRC_DC_GATHER(true, 2);
+    else if (gs.perm) NRC_DC_GATHER(false, 1);
+    else NRC_DC_GATHER(false, 2);
+#undef NRC_DC_GATHER
+    return hipGetLastError();
 }
 
 }  // namespace nrc_amd

@@ -11,6 +11,7 @@ reference                                            here
 ``propagate_train_radiance`` (:131)                  ``propagate_train_radiance``
 ``generateRandomPermutationForTrain`` (NRCUtil.cu)   ``generate_train_permutation``
 ``permute_train_data`` (:226)                        ``permute_train_data``
+``permute_train_data`` + ``Network::train``          ``train_gather`` (the copy fused away)
 ``Device::render`` post-trace sequence               ``process_frame``
 ===================================================  ==============================================
 
@@ -96,6 +97,7 @@ def _sigs():
         "nrc_copy_radiance_to_output_factored_padded": [vp, vp, vp, u32, vp],
         "nrc_propagate_train_radiance_factored_padded": [vp, vp, vp, u32, vp, vp, vp, u32, vp],
         "nrc_permute_train_data_padded": [vp, vp, vp, u64, u32, i32, vp, vp, u32, vp],
+        "nrc_train_gather": [vp, vp, vp, vp, u64, u32, i32, u32, u32, u32, vp],
         "nrc_process_frame": [vp, ctypes.POINTER(NrcFrameBuffers), ctypes.POINTER(NrcFrameParams),
                               ctypes.POINTER(ctypes.c_float)],
         "nrc_process_frame_shard": [vp, ctypes.POINTER(NrcFrameBuffers), ctypes.POINTER(NrcFrameParams), u32, u32,
@@ -229,6 +231,18 @@ def permute_train_data(queries_src, targets_src, permutation, seed: int, frame_i
     check(fn(_ptr(queries_src, "queries_src"), _ptr(targets_src, "targets_src"), _ptr(permutation, "permutation"),
              int(seed), int(frame_index), int(num_records), _ptr(queries_dst, "queries_dst"),
              _ptr(targets_dst, "targets_dst"), int(n_out), _stream(stream)))
+
+
+def train_gather(net, queries_src, targets_src, permutation, seed: int, frame_index: int, num_records: int,
+                 first: int, b: int, n_out: int = NUM_TRAINING_RECORDS_PER_FRAME, loss=None) -> None:
+    """One optimizer step on samples gathered from the traced buffers: sample d is record
+    perm(first + d) % min(num_records, n_out), perm as permute_train_data() defines it -- bit for bit
+    permute_train_data() followed by net.train_async() on rows [first, first + b) of its output, without the copy
+    (frame.h nrc_train_gather). On the network's stream; ``loss``: a device float slot or None. Width 64, Frequency
+    (compact or padded per the network's query layout); other handles raise NrcError (NRC_ERR_UNSUPPORTED)."""
+    check(_sigs().nrc_train_gather(net._h, _ptr(queries_src, "queries_src"), _ptr(targets_src, "targets_src"),
+                                   _ptr(permutation, "permutation"), int(seed), int(frame_index), int(num_records),
+                                   int(n_out), int(first), int(b), _ptr(loss, "loss")))
 
 
 def records_to_device(arr: np.ndarray, device):
