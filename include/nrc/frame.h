@@ -117,6 +117,40 @@ nrc_status nrc_infer_accumulate_factored(nrc_net* net, const float* queries_d, f
                                          const nrc_float3* end_render_throughput_d, float* output_rgba_d,
                                          uint32_t num_pixels, int mode, uint32_t iteration_index);
 
+/* Fused accumulation that culls the zero-throughput render queries before the network runs: the skip of
+ * nrc_infer_accumulate_sparse on F16 and FP8 handles, with plain (reflectance_factoring 0: nrc_infer_accumulate's
+ * epilogue) or reflectance-factored (non-zero: nrc_infer_accumulate_factored's) accumulation. Three launches on the
+ * handle's stream: a streaming liveness pass over the throughputs that also finishes the dead pixels, a pack of the
+ * live rows, and the dense kernel walking the packed rows and the queries [num_pixels, n). Inference (EMA) weights.
+ * Arguments and argument checks of nrc_infer_accumulate, plus: mode is Full or CacheOnly (any other mode, mode 4
+ * included -- it has no throughput to cull by -- is NRC_ERR_INVALID_ARGUMENT); n <= 2^26, else
+ * NRC_ERR_INVALID_ARGUMENT.
+ * Liveness: a render query i < num_pixels is dead iff all three words of T = end_render_throughput_d[i] have
+ * (bits & 0x7fffffff) == 0: +-0 is dead, NaN and denormals are live (the set of the sparse entry's IEEE rule). Queries
+ * [num_pixels, n) are always live.
+ * Live queries: bit for bit the results of the dense entry on the same handle -- nrc_infer_accumulate for
+ * reflectance_factoring 0, nrc_infer_accumulate_factored otherwise -- in output_rgba_d and results_d[num_pixels, n).
+ * Dead pixels, in both factoring settings: Full dst.c = fmaf(T.c * 0.0f, w, dst.c), CacheOnly dst.c = 0.0f * T.c,
+ * dst.w = 1; their query record is never read. That equals the dense result bitwise whenever the dense radiance is
+ * finite and, with factoring, every reflectance component is finite with its sign bit clear. The deviations: where the
+ * dense radiance is inf (f16 overflow of the output) or, with factoring, a reflectance component is non-finite, the
+ * dense path writes NaN and this one does not; where a reflectance component is negative, the dense path's zero has
+ * the opposite sign.
+ * results_d[0, num_pixels) is never written; nothing is read or written past n; num_pixels may be 0 or n.
+ * Workspace: the handle owns a uint32 row list of num_pixels entries with per-segment counts and a total, allocated on
+ * the first call and grown on the first call with more pixels, freed by nrc_destroy. A call that grows it allocates
+ * device memory (and waits for the stream first if it replaces a smaller one), so it cannot be captured into a graph;
+ * calls that fit the workspace only launch.
+ * Handles: width 64, NRC_ENCODING_FREQUENCY, compact queries, infer_precision NRC_PRECISION_F16 or NRC_PRECISION_FP8.
+ * Every other handle (Hash, FrequencySH, padded queries, NRC_PRECISION_F16_ACC16, width 128) is NRC_ERR_UNSUPPORTED with
+ * a message that names the combination. nrc_process_frame / nrc_process_frame_shard take this entry for their Full /
+ * CacheOnly render + tile inference, passing reflectance_factoring through, when the process-wide knob "frame_culled"
+ * is 1, keep_render_results is 0 and the handle is supported (nrc_c.h). */
+nrc_status nrc_infer_accumulate_culled(nrc_net* net, const float* queries_d, float* results_d, uint32_t n,
+                                       const nrc_float3* end_render_throughput_d, float* output_rgba_d,
+                                       uint32_t num_pixels, int mode, uint32_t iteration_index,
+                                       int reflectance_factoring);
+
 /* copy_radiance_to_output_buffer (nrc_helpers.cu:54-73): out = (radiance, 1) for n pixels. */
 nrc_status nrc_copy_radiance_to_output(const nrc_float3* radiance_d, float* output_rgba_d, uint32_t num_pixels,
                                        hipStream_t stream);

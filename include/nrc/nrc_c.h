@@ -253,7 +253,10 @@ nrc_status nrc_set_step(nrc_net* net, uint32_t step);
  * infer + the factored accumulation kernel; range -1..1), "frame_train_gather" (nrc_process_frame / _shard: 1 = no
  * permute_train_data launch, the minibatch steps gather their samples from the traced buffers through nrc_train_gather
  * on handles it serves, outside data-parallel mode, frame.h; the shuffled [1] buffers are then not written; -1 / 0
- * permute, then train; range -1..1); debug library only: "dc_dw0_delay", "hash_feat_abl".
+ * permute, then train; range -1..1), "frame_culled" (nrc_process_frame / _shard: 1 = the Full / CacheOnly render + tile
+ * inference through nrc_infer_accumulate_culled, plain or reflectance-factored, on handles it supports and with
+ * keep_render_results 0, frame.h; it comes ahead of frame_sparse and frame_factored_fused; -1 / 0 off; range -1..1);
+ * debug library only: "dc_dw0_delay", "hash_feat_abl".
  * -1 restores the production choice. A value outside a knob's range (train_kernel -1/0/1/2/32,
  * train_shape -1..7, scatter_min / scatter_max -1 or 16..2^20, hash_infer -1..1, t16_groups -1/1/2, dc_dw0_delay -1..2^20, hash_feat_abl
  * -1..36, hash_feat_p -1 or a multiple of 8 in 8..256, peer_path -1..4, px_polls -1 or 1..2^21, scatter_part / scatter_compact -1..16, hash_train_feat -1..1, hash_adam -1..0) is

@@ -51,7 +51,7 @@ EXPORTS = [
     "nrc_debug_encode_fast_variant", "nrc_debug_infer_precision", "nrc_debug_fp8_convert", "nrc_debug_set_knob",
     "nrc_debug_get_knob", "nrc_debug_set_peer_seq",
     # include/nrc/frame.h (bound in frame.py)
-    "nrc_accumulate_render_radiance", "nrc_infer_accumulate", "nrc_infer_accumulate_sparse", "nrc_infer_accumulate_factored", "nrc_copy_radiance_to_output", "nrc_propagate_train_radiance",
+    "nrc_accumulate_render_radiance", "nrc_infer_accumulate", "nrc_infer_accumulate_sparse", "nrc_infer_accumulate_factored", "nrc_infer_accumulate_culled", "nrc_copy_radiance_to_output", "nrc_propagate_train_radiance",
     "nrc_accumulate_render_radiance_factored", "nrc_copy_radiance_to_output_factored", "nrc_propagate_train_radiance_factored",
     "nrc_accumulate_render_radiance_factored_padded", "nrc_copy_radiance_to_output_factored_padded",
     "nrc_propagate_train_radiance_factored_padded", "nrc_permute_train_data_padded",

@@ -264,13 +264,14 @@ bool want_t16(int encoding) {
     return encoding == NRC_ENCODING_FREQUENCY || encoding == NRC_ENCODING_HASH;
 }
 
-std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+std::atomic<int> g_knobs[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 const char* const kKnobNames[kKnobCount] = {"train_kernel", "train_shape", "scatter_min", "scatter_max", "dc_dw0_delay",
                                             "hash_infer", "hash_feat_abl", "t16_groups", "hash_feat_p", "peer_path",
                                             "px_polls", "scatter_part", "scatter_compact", "hash_train_feat",
                                             "hash_adam", "train_fused", "fuse_mode", "tcnn_reentry", "train_prio",
-                                            "frame_sparse", "frame_factored_fused", "frame_train_gather"};
-static_assert(kKnobCount == 22, "one initial value and one name per knob");
+                                            "frame_sparse", "frame_factored_fused", "frame_train_gather",
+                                            "frame_culled"};
+static_assert(kKnobCount == 23, "one initial value and one name per knob");
 
 std::string config_json(int encoding, const nrc_config& c) {
     char buf[2048];
@@ -373,6 +374,8 @@ struct nrc_net {
     float* dp_grad = nullptr;        // [grad_floats] gradient exchange buffer of nrc_train_dp
     void* frame_scratch = nullptr;   // frame driver scratch (net_frame_scratch): the key sort's permutation + temp
     size_t frame_scratch_bytes = 0;
+    uint32_t* cull_ws = nullptr;     // nrc_infer_accumulate_culled: row lists, segment counts and the live total of
+    uint32_t cull_ws_pixels = 0;     // cull_ws_pixels pixels (cull_workspace_bytes); grown on demand
     float* loss_dev = nullptr;   // device view of loss_host
     float* loss_host = nullptr;
     // training-protocol error word (round 4), in the same mapped allocation as the loss slots (index kProtoErrSlot):
@@ -529,6 +532,9 @@ struct nrc_net {
         f(frame_scratch);
         frame_scratch = nullptr;
         frame_scratch_bytes = 0;
+        f(cull_ws);
+        cull_ws = nullptr;
+        cull_ws_pixels = 0;
         f(grid_grad); f(grid_steps); f(grid_bias); f(table_train); f(table_infer); f(hash_feat);
         hash_feat = nullptr;
         if (feat_done) (void)hipEventDestroy(feat_done);
@@ -1054,6 +1060,23 @@ bool nrc_amd::net_infer_factored_ok(nrc_net* net) {
     return factored_unsupported(net) == nullptr;
 }
 
+// why nrc_infer_accumulate_culled cannot serve the handle (names the combination), or null
+static const char* culled_unsupported(nrc_net* net) {
+    if (net->wide()) return "culled fused accumulation: width 128 is not supported (width 64 only)";
+    if (net->hash()) return "culled fused accumulation: InputEncoding::Hash is not supported (Frequency only)";
+    if (net->encoding == NRC_ENCODING_FREQUENCY_SH)
+        return "culled fused accumulation: InputEncoding::FrequencySH is not supported (Frequency only)";
+    if (net->cfg.infer_precision == NRC_PRECISION_F16_ACC16)
+        return "culled fused accumulation: NRC_PRECISION_F16_ACC16 is not supported (F16 and FP8 only)";
+    if (net->padq()) return "culled fused accumulation: padded queries are not supported (compact only)";
+    return nullptr;
+}
+
+bool nrc_amd::net_infer_culled_ok(nrc_net* net) {
+    check_live(net);
+    return culled_unsupported(net) == nullptr;
+}
+
 bool nrc_amd::net_train_gather_ok(nrc_net* net, uint32_t b) {
     check_live(net);
     return train_gather_unsupported(net, b) == nullptr;
@@ -1102,6 +1125,7 @@ bool knob_value_ok(Knob k, int v) {
         case kKnobFrameSparse: return v >= -1 && v <= 1;
         case kKnobFrameFactoredFused: return v >= -1 && v <= 1;
         case kKnobFrameTrainGather: return v >= -1 && v <= 1;
+        case kKnobFrameCulled: return v >= -1 && v <= 1;
         default: return false;
     }
 }
@@ -1475,6 +1499,38 @@ nrc_status nrc_infer_accumulate_factored(nrc_net* net, const float* in, float* o
         else
             HIP_CHECK(launch_infer_accumulate_factored(in, out, n, net->wf_infer, reinterpret_cast<const float*>(thr),
                                                        rgba, num_pixels, mode, w, net->stream));
+    });
+}
+
+nrc_status nrc_infer_accumulate_culled(nrc_net* net, const float* in, float* out, uint32_t n, const nrc_float3* thr,
+                                       float* rgba, uint32_t num_pixels, int mode, uint32_t iteration_index,
+                                       int reflectance_factoring) {
+    return guarded([&] {
+        check_live(net);
+        if (mode != NRC_RENDER_FULL && mode != NRC_RENDER_CACHE_ONLY)
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "culled fused accumulation supports RenderMode Full and CacheOnly only");
+        if (num_pixels > n) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "num_pixels > n");
+        if (n > kCullMaxQueries) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "culled fused accumulation: n must be <= 2^26");
+        if (const char* why = culled_unsupported(net)) throw ApiError(NRC_ERR_UNSUPPORTED, why);
+        if (n == 0) return;
+        if (!in || (num_pixels < n && !out)) throw ApiError(NRC_ERR_INVALID_ARGUMENT, "null query/result pointer");
+        if (num_pixels > 0 && (!thr || !rgba || (reinterpret_cast<uintptr_t>(rgba) & 15)))
+            throw ApiError(NRC_ERR_INVALID_ARGUMENT, "throughput / 16-byte aligned float4 frame buffer required");
+        if (!net->cull_ws || num_pixels > net->cull_ws_pixels) {  // grow: allocates (not capturable into a graph)
+            if (net->cull_ws) {
+                HIP_CHECK(hipStreamSynchronize(net->stream));  // a queued kernel may still use the old workspace
+                HIP_CHECK(hipFree(net->cull_ws));
+            }
+            net->cull_ws = nullptr;
+            net->cull_ws_pixels = 0;
+            HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&net->cull_ws), cull_workspace_bytes(num_pixels)));
+            net->cull_ws_pixels = num_pixels;
+        }
+        const float w = 1.0f / (float)(iteration_index + 1u);  // nrc_helpers.cu:98
+        HIP_CHECK(launch_infer_accumulate_culled(in, out, n, net->wf_infer, net->fp8_64() ? net->img8 : nullptr,
+                                                 reinterpret_cast<const float*>(thr), rgba, num_pixels, mode, w,
+                                                 reflectance_factoring != 0, net->cull_ws, net->cull_ws_pixels,
+                                                 net->stream));
     });
 }
 

@@ -1,7 +1,8 @@
 // nrc_chain47.h — the f16 chain of the product inference kernel (variant 47 of nrc_kernels.hip) for one 32-query tile,
-// shared by the kernels built around it outside that unit (nrc_infer_sparse.hip, nrc_infer_factored.hip): the same
-// 32x32x16 f16 MFMAs in the same K order per layer, the 4x4x4 output layer and the permlane32 half sums, so the
-// radiance is bit-identical to nrc_infer's. Weights: the handle's f16 inference image, resident in LDS.
+// shared by the kernels built around it outside that unit (nrc_infer_sparse.hip, nrc_infer_factored.hip,
+// nrc_infer_culled.hip): the same 32x32x16 f16 MFMAs in the same K order per layer, the 4x4x4 output layer and the
+// permlane32 half sums, so the radiance is bit-identical to nrc_infer's. Weights: the handle's f16 inference image,
+// resident in LDS.
 #pragma once
 
 #include "nrc_device.h"

@@ -235,13 +235,21 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
     const bool rf_fused = rf && !p->keep_render_results && knob(kKnobFrameFactoredFused) == 1 &&
                           net_infer_factored_ok(net);
     const bool rf_fuse = rf_fused && (mode == NRC_RENDER_FULL || mode == NRC_RENDER_CACHE_ONLY);
+    // knob "frame_culled": zero-throughput pixels are culled before the MLP (nrc_infer_accumulate_culled), plain or
+    // factored, on handles it supports; ahead of frame_sparse and frame_factored_fused
+    const bool culled = !p->keep_render_results && (mode == NRC_RENDER_FULL || mode == NRC_RENDER_CACHE_ONLY) &&
+                        knob(kKnobFrameCulled) == 1 && net_infer_culled_ok(net);
     if ((uint64_t)screen + tiles > 0) require(qi && ri, "inference buffers are NULL");
     auto infer_range = [&](uint32_t first, uint32_t count, uint32_t acc_pixels) {
         // queries [first, first + count); the first acc_pixels of them are render queries of pixels first..
         if (count == 0) return;
         const float* q = qi + (size_t)first * QD;
         float* r = reinterpret_cast<float*>(ri + first);
-        if (fuse && acc_pixels > 0 && sparse)
+        if (culled && acc_pixels > 0 && count <= kCullMaxQueries)
+            check(nrc_infer_accumulate_culled(net, q, r, count, fb->last_render_throughput_d + first,
+                                              fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode,
+                                              p->iteration_index, rf ? 1 : 0));
+        else if (fuse && acc_pixels > 0 && sparse)
             check(nrc_infer_accumulate_sparse(net, q, r, count, fb->last_render_throughput_d + first,
                                               fb->output_rgba_d + (size_t)first * 4, acc_pixels, mode,
                                               p->iteration_index));
@@ -262,7 +270,8 @@ void process_frame(nrc_net* net, const nrc_frame_buffers* fb, const nrc_frame_pa
         infer_range(screen, tiles, 0);
     }
     // Device::nrcAccumulateRadiance (Device.cpp:1310-1337)
-    if (!skip_render && !fuse && !rf_fuse && npix > 0) {
+    const bool culled_done = culled && npix > 0 && (whole ? screen + tiles : npix) <= kCullMaxQueries;
+    if (!skip_render && !fuse && !rf_fuse && !culled_done && npix > 0) {
         if (rf)
             check(accumulate_factored(fb->results_inference_d + p0, qi + (size_t)p0 * QD, fb->last_render_throughput_d + p0,
                                       fb->output_rgba_d + (size_t)p0 * 4, npix, mode, p->iteration_index, s, padq));

@@ -290,6 +290,17 @@ hipError_t launch_infer_accumulate_sparse(const float* queries, float* out, int6
 hipError_t launch_infer_accumulate_factored(const float* queries, float* out, int64_t n, const _Float16* wf,
                                             const float* thr, float* rgba, int64_t n_acc, int mode, float w,
                                             hipStream_t s);
+// fused accumulation behind a cull of the zero-throughput render queries (nrc_infer_culled.hip): width 64, Frequency,
+// compact queries; img8 = the FP8 image of an FP8 handle, null for F16; mode 0 Full / 2 CacheOnly; factored = the
+// reflectance-factored epilogue. Three launches on s: classify (a wave per kCullSegment pixels), pack, tiles.
+// ws: cull_workspace_bytes(ws_pixels) bytes of device memory, ws_pixels >= npix; n <= kCullMaxQueries.
+constexpr int kCullSegment = 2048;
+constexpr uint32_t kCullMaxQueries = 1u << 26;  // 60 n and 16 npix stay below 2^32, every descriptor below 2^31 bytes
+constexpr uint32_t cull_segments(uint32_t pixels) { return (pixels + kCullSegment - 1) / kCullSegment; }
+size_t cull_workspace_bytes(uint32_t pixels);
+hipError_t launch_infer_accumulate_culled(const float* queries, float* out, uint32_t n, const _Float16* wf,
+                                          const uint8_t* img8, const float* thr, float* rgba, uint32_t npix, int mode,
+                                          float w, bool factored, uint32_t* ws, uint32_t ws_pixels, hipStream_t s);
 // InputEncoding::Hash inference (mode -1: plain; 0 / 2: fused accumulation for queries [0, n_acc))
 // feat: the handle's [NRC_HASH_LEVELS][kHashFeatStride] level-feature workspace (hash_feature_kernel, round 3), or
 // nullptr for the round-2 gather kernel (also knob "hash_infer" = 1)
@@ -456,7 +467,10 @@ enum Knob : int {
     kKnobFrameTrainGather = 21,    // nrc_process_frame / _shard: 1 = no permute_train_data launch, the NUM_BATCHES steps
                                    // gather from the traced buffers (nrc_train_gather) on handles it serves, outside
                                    // data-parallel mode (-1 / 0: permute, then train on the shuffled buffers)
-    kKnobCount = 22
+    kKnobFrameCulled = 22,         // nrc_process_frame / _shard: 1 = the Full / CacheOnly render + tile launch through
+                                   // nrc_infer_accumulate_culled (plain or factored) on handles it supports, ahead of
+                                   // frame_sparse and frame_factored_fused (-1 / 0: off)
+    kKnobCount = 23
 };
 int knob(Knob k);
 
@@ -592,6 +606,8 @@ bool net_infer_fusable(nrc_net* net);
 bool net_infer_sparse_ok(nrc_net* net);
 // nrc_infer_accumulate_factored serves the handle (width 64, Frequency, F16 or FP8, compact queries)
 bool net_infer_factored_ok(nrc_net* net);
+// nrc_infer_accumulate_culled serves the handle (width 64, Frequency, F16 or FP8, compact queries)
+bool net_infer_culled_ok(nrc_net* net);
 // nrc_train_gather serves a b-sample step of the handle (width 64, Frequency, the production training kernels)
 bool net_train_gather_ok(nrc_net* net, uint32_t b);
 // throws NRC_ERR_INTERNAL if a training kernel or a peer-exchange wait reported a timeout (after a stream sync)

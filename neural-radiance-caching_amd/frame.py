@@ -86,6 +86,7 @@ def _sigs():
         "nrc_infer_accumulate": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
         "nrc_infer_accumulate_sparse": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
         "nrc_infer_accumulate_factored": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32],
+        "nrc_infer_accumulate_culled": [vp, vp, vp, u32, vp, vp, u32, ctypes.c_int, u32, ctypes.c_int],
         "nrc_propagate_train_radiance": [vp, vp, u32, vp, vp, u32, vp],
         "nrc_accumulate_render_radiance_factored": [vp, vp, vp, vp, u32, ctypes.c_int, u32, vp],
         "nrc_copy_radiance_to_output_factored": [vp, vp, vp, u32, vp],
@@ -185,6 +186,19 @@ def infer_accumulate_factored(net, queries, results, n: int, throughput, output_
     check(_sigs().nrc_infer_accumulate_factored(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
                                                 _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
                                                 int(num_pixels), int(mode), int(iteration_index)))
+
+
+def infer_accumulate_culled(net, queries, results, n: int, throughput, output_rgba, num_pixels: int, mode: RenderMode,
+                            iteration_index: int, reflectance_factoring: bool = False) -> None:
+    """Fused accumulation that culls the render queries whose throughput words are all +-0 before the network runs
+    (frame.h): live queries are bit-identical to infer_accumulate() / (``reflectance_factoring``)
+    infer_accumulate_factored(), dead pixels get the dense epilogue's value for radiance +0. Modes Full and CacheOnly,
+    n <= 2^26. Width 64, Frequency, F16 or FP8, compact queries; other handles raise NrcError (NRC_ERR_UNSUPPORTED).
+    The handle's workspace grows on the first call with more pixels (that call allocates)."""
+    check(_sigs().nrc_infer_accumulate_culled(net._h, _ptr(queries, "queries"), _ptr(results, "results"), int(n),
+                                              _ptr(throughput, "throughput"), _ptr(output_rgba, "output_rgba"),
+                                              int(num_pixels), int(mode), int(iteration_index),
+                                              int(bool(reflectance_factoring))))
 
 
 def copy_radiance_to_output(radiance, output_rgba, num_pixels: int, stream=None) -> None:
